@@ -28,7 +28,14 @@ barriers, as the driver's contract asks.  Every step is also bracketed by its ow
 (topo_amd_mark): `ms_per_step_median` / `_mean` / `_min` / `_max` are those per-launch durations,
 and the roofline uses their mean.  Before the W warm-up steps the clocks are brought up by untimed
 launches until three consecutive ones agree within 1.5 % (`clock_ramp_steps`; the first ~8 launches
-after an idle period run up to 25 % slow), so that W = 5 and W = 10 give the same number.
+after an idle period run up to 25 % slow), so that W = 5 and W = 10 give the same number.  The library keeps 512
+numbered events: beyond 510 steps the events bracket groups of consecutive steps, and the per-step figures are
+the groups' durations over their step counts (`steps_per_mark`).
+
+--dump-outputs DIR writes what the last timed step computed - the TPI plane - as float32 rows of a fixed, seeded
+sample (every row when the plane is small) with their global row indices; the synthetic DEM is the same in every
+run, so two builds can be compared output for output.  With N > 1 every rank writes the sampled rows it owns
+(tpi_rank<r>.npy, tpi_rows_rank<r>.npy).
 """
 import argparse
 import json
@@ -60,6 +67,9 @@ def parse():
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="skip the host-buffer end_to_end section (it launches the headline kernel on a 16384^2 DEM: under "
                          "rocprofv3 --stats those launches would enter the kernel's average duration)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the TPI plane of the last step as DIR/tpi.npy (a fixed, seeded "
+                         "sample of whole rows, at most 32 MB) and their row indices as DIR/tpi_rows.npy")
     return ap.parse_args()
 
 
@@ -167,6 +177,29 @@ def stats(ms):
     n = len(ms)
     med = ms[n // 2] if n % 2 else 0.5 * (ms[n // 2 - 1] + ms[n // 2])
     return {"median": med, "mean": sum(ms) / n, "min": ms[0], "max": ms[-1], "n": n}
+
+
+DUMP_BYTES = 32 << 20  # the sample of the TPI plane --dump-outputs writes
+
+
+def dump_outputs(path, out, row0, ny, nx, rank, world):
+    """Write the sampled rows of the TPI plane `out` (this rank's rows row0 .. row0 + out.rows of the ny x nx DEM)
+    and their global row indices.  The sample depends on (ny, nx) only, not on the build or the number of ranks."""
+    if nx * 4 > DUMP_BYTES:
+        sys.exit(f"bench.py --dump-outputs: one row of {nx} columns is more than {DUMP_BYTES >> 20} MB")
+    n = min(ny, DUMP_BYTES // (nx * 4))
+    rows = np.arange(ny) if n == ny else np.sort(np.random.default_rng(20260).choice(ny, n, replace=False))
+    mine = rows[(rows >= row0) & (rows < row0 + out.rows)]
+    if len(mine) == out.rows:
+        tpi = out.to_host()
+    else:
+        tpi = np.empty((len(mine), nx), np.float32)
+        for i, r in enumerate(mine):
+            tpi[i] = out.to_host(int(r) - row0, 1)[0]
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"tpi{suffix}.npy"), tpi)
+    np.save(os.path.join(path, f"tpi_rows{suffix}.npy"), mine.astype(np.float64))
 
 
 def time_kernel(fn, reps, dev):
@@ -658,20 +691,26 @@ def main():
     d.sync()
     rdv.barrier()
     steps = args.steps
-    if steps > 510:
-        sys.exit("bench.py: at most 510 timed steps (one HIP event per step)")
+    if steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    stride = -(-steps // 510)  # steps between two HIP events: 1 up to 510 steps (the library keeps 512 events)
     t0 = time.perf_counter()
     d.mark(0)
+    marks = [0]  # steps done at each recorded event
     for k in range(steps):
         step()
-        d.mark(k + 1)  # HIP events on the compute stream between the K launches, no host synchronise
+        if (k + 1) % stride == 0 or k + 1 == steps:
+            d.mark(len(marks))  # HIP events on the compute stream between the launches, no host synchronise
+            marks.append(k + 1)
     d.sync()
     rdv.barrier()
     wall = time.perf_counter() - t0
     wall = rdv.max(wall)
-    per_step = stats([d.mark_elapsed(k, k + 1) for k in range(steps)])
+    per_step = stats([d.mark_elapsed(i, i + 1) / (marks[i + 1] - marks[i]) for i in range(len(marks) - 1)])
     kernel_ms = rdv.max(per_step["mean"])
     kernel_ms_median = rdv.max(per_step["median"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, row0, ny, nx, rank, world)
 
     px_total = ny * nx
     value = px_total * args.steps / wall / 1e6
@@ -691,6 +730,7 @@ def main():
             "ms_per_step_mean": round(kernel_ms, 4),
             "ms_per_step_min": round(per_step["min"], 4),
             "ms_per_step_max": round(per_step["max"], 4),
+            "steps_per_mark": stride,
             "value_at_median": round(px_total / kernel_ms_median / 1e3, 1),
             "clock_ramp_steps": ramp,
             "higher_is_better": True,
