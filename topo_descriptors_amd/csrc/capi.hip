@@ -506,26 +506,6 @@ int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float*
     return launch_tpi_std(d, disc, tpi_out, std_out);
 }
 
-// ghost rows the gradient cannot do without: the filter radius plus the row of the central difference
-int gradient_halo(double sigma, double sig_ratio) {
-    if (sigma <= 1.0) return 1;
-    const double s_max = sig_ratio == 1.0 ? sigma : std::max(sigma, sigma * sig_ratio);
-    return gaussian_radius(s_max) + 1;
-}
-
-// ghost rows a row SHARD of the gradient is laid out with and exchanges: what topo_amd_halo_rows(GRADIENT)
-// answers and what topo_amd_shard_gradient uses (one function, so the two cannot drift apart).  Radii
-// mfma_min_radius(true) .. 15 of the isotropic smooth ask for 17 rows: the matrix-core kernels take their
-// accumulation offsets 16 rows into a 32-row tile (gauss.hip, mfma_rows_ok), and with R + 1 rows the interior and
-// the seam strips of a shard would mix matrix-core and vector-ALU kernels depending on row0 % 32.
-int gradient_shard_halo(double sigma, double sig_ratio) {
-    if (sigma <= 1.0) return 1;
-    if (sig_ratio == 0.0) sig_ratio = 1.0;
-    if (sig_ratio != 1.0) return gradient_halo(sigma, sig_ratio);
-    const int R = gaussian_radius(sigma);
-    return (R >= mfma_min_radius(true) && R < 16) ? 17 : R + 1;
-}
-
 // RAII-less helper for the host-buffer entry points
 // Device buffers of one host-buffer call, and the preparation of its result arrays.  A result array
 // fresh from the allocator has no pages yet; faulting them in one by one under the download is what a
@@ -1285,21 +1265,16 @@ int topo_amd_halo_rows(int descriptor, double p0, double p1, int* above, int* be
         case TOPO_AMD_DESC_STD: {
             DiscRuns d;
             TOPO_TRY(build_disc((int)p0, &d));
-            int R = p1 > 0.0 ? gaussian_radius(p1) : 0;
-            if (R >= mfma_min_radius(false) && R < 16) R = 16;  // pre-smoothing on the matrix cores: see DESC_GAUSS
+            const int R = p1 > 0.0 ? gauss_ghost_rows(p1) : 0;  // the pre-smoothing
             *above = -d.dj_min + R;
             *below = d.dj_max + R;
             return TOPO_AMD_OK;
         }
-        case TOPO_AMD_DESC_GAUSS: {
-            // (radius mfma_min_radius .. 15: the matrix-core kernels want the accumulation-offset row of every
-            // 32-row tile inside the block, 16 rows from the tile's first row: gauss.hip, mfma_rows_ok)
-            const int R = gaussian_radius(p0);
-            *above = *below = (R >= mfma_min_radius(false) && R < 16) ? 16 : R;
+        case TOPO_AMD_DESC_GAUSS:
+            *above = *below = gauss_ghost_rows(p0);
             return TOPO_AMD_OK;
-        }
         case TOPO_AMD_DESC_GRADIENT:
-            *above = *below = gradient_shard_halo(p0, p1);
+            *above = *below = gradient_ghost_rows(p0, p1, false);
             return TOPO_AMD_OK;
         case TOPO_AMD_DESC_SOBEL:
             *above = *below = 1;
@@ -1398,7 +1373,7 @@ int topo_amd_gradient_dev(const float* in, int in_rows, int in_row0, int gny, in
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
-    const int h = gradient_halo(sigma, sig_ratio);
+    const int h = gradient_ghost_rows(sigma, sig_ratio, true);
     TOPO_TRY(check_block(b, h, h, "gradient"));
     ClassScope cls(b);
     for (float* o : {dx_out, dy_out, slope_out, aspect_out}) forget_plane(o, out_rows, nx);
@@ -1617,7 +1592,7 @@ int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double
         rx = d_rx;
         ry = d_ry;
     }
-    const int h = gradient_halo(sigma, sig_ratio == 0.0 ? 1.0 : sig_ratio);
+    const int h = gradient_ghost_rows(sigma, sig_ratio, true);
     std::vector<HostPlane> outs;
     for (int k = 0; k < 4; ++k) outs.push_back({host_out[k], (float*)d_o[k]});
     return run_pipelined(run, dem, (float*)d_in, ny, nx, h, h, true, outs, [&](int view_rows, int r0, int rows) {
@@ -2211,7 +2186,7 @@ int topo_amd_shard_gradient(float* block, int rows_local, int row0, int gny, int
                             float* dx_out, float* dy_out, float* slope_out, float* aspect_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    const int h = gradient_shard_halo(sigma, sig_ratio);  // == topo_amd_halo_rows(GRADIENT, sigma, sig_ratio)
+    const int h = gradient_ghost_rows(sigma, sig_ratio, false);  // == topo_amd_halo_rows(GRADIENT, sigma, sig_ratio)
     TOPO_TRY(shard_view(&block, h, h, "shard_gradient"));
     block += shard_view_offset(h, nx);
     Shard s = make_shard(block, rows_local, row0, gny, nx, h, h);

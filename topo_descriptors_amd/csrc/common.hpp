@@ -189,9 +189,14 @@ int launch_tpi_pair(const Block& b, int size_a, float* out_a, int size_b, float*
 bool tpi_pair_covers(int size_a, int size_b);
 // any size: float64 column prefix sums in HBM (slow, exact)
 int launch_disc_big(const Block& b, const DiscRuns& disc, float* tpi_out, float* std_out);
-int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out, bool small_ok = true);
-// smallest radius that takes the matrix-core Gaussian kernels (>= 8); below 16 they want 16 ghost rows
-int mfma_min_radius(bool for_gradient);
+int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out);
+// ghost rows a row block carries above and below for the Gaussian of sigma: the radius, or 16 for the radii below 16
+// that take the matrix-core kernels (they want the accumulation-offset row of every 32-row tile inside the block)
+int gauss_ghost_rows(double sigma);
+// ... for the gradient (sig_ratio 0 counts as 1): the wider smooth's radius plus the row of the central difference,
+// 1 for sigma <= 1 (Sobel).  least: the fewest a block may come with; otherwise what topo_amd_halo_rows(GRADIENT) and a
+// row shard use, 17 for the isotropic matrix-core radii below 16, at which every row block takes the whole raster's kernels
+int gradient_ghost_rows(double sigma, double sig_ratio, bool least);
 int launch_sobel(const Block& b, float* dx_out, float* dy_out);
 int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode,
                     const void* res_x, const void* res_y, float* dx, float* dy, float* slope,

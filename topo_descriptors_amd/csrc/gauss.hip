@@ -1827,14 +1827,24 @@ __global__ __launch_bounds__(64) void gauss_f16_repair_kernel(GaussArgs p, int u
 // repair passes: one wave per block; enough blocks to fill the chip when many tiles are marked (a DEM with a NaN sea),
 // a short scan of the marks when none is
 constexpr long kRepairBlocks = 8192;
-int upload_weights(int slot, double sigma, int kb, GaussArgs* a) {
+
+// the float64 taps exp(-k^2 / 2 sigma^2), k = -R ... R (R = gaussian_radius(sigma)), into *w if given; returns their sum
+double gauss_taps(double sigma, std::vector<double>* w = nullptr) {
     const int R = gaussian_radius(sigma);
-    std::vector<double> w(2 * R + 1);
+    if (w) w->resize(2 * R + 1);
     double sum = 0.0;
     for (int k = -R; k <= R; ++k) {
-        w[k + R] = std::exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
-        sum += w[k + R];
+        const double t = std::exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
+        if (w) (*w)[k + R] = t;
+        sum += t;
     }
+    return sum;
+}
+
+int upload_weights(int slot, double sigma, int kb, GaussArgs* a) {
+    const int R = gaussian_radius(sigma);
+    std::vector<double> w;
+    const double sum = gauss_taps(sigma, &w);
     const int nchunks = (2 * R + 1 + kb - 1) / kb;
     std::vector<float> padded((size_t)nchunks * kb, 0.0f);
     for (int k = 0; k <= 2 * R; ++k) padded[k] = (float)(w[k] / sum);
@@ -1862,6 +1872,39 @@ int upload_weights(int slot, double sigma, int kb, GaussArgs* a) {
     return TOPO_AMD_OK;
 }
 
+// the arguments of a pass over block b into `out`, with the taps of sigma in table slot `slot` (chunks of kb taps; kb == 1:
+// the plain taps and the slab table)
+int gauss_args(const Block& b, float* out, double sigma, int kb, int slot, GaussArgs* a) {
+    *a = GaussArgs{};
+    a->in = b.in;
+    a->out = out;
+    a->in_rows = b.in_rows;
+    a->in_row0 = b.in_row0;
+    a->gny = b.gny;
+    a->nx = b.nx;
+    a->out_row0 = b.out_row0;
+    a->out_rows = b.out_rows;
+    return upload_weights(slot, sigma, kb, a);
+}
+// a plane of `rows` rows taken as a raster of its own
+Block plane_block(const float* in, int rows, int nx) { return Block{in, rows, 0, rows, nx, 0, rows}; }
+
+// the cut of each of `lines` lines of `ntile` tiles into at most max(1, max_runs) runs with the least rounds x (tiles per
+// run + the `halo` tiles a run restages), `slots` lines running at once
+int run_cut(long lines, int ntile, int max_runs, long slots, int halo) {
+    int nseg = 1;
+    long best = -1;
+    for (int n = 1; n <= std::max(1, max_runs); ++n) {
+        const long rounds = (lines * n + slots - 1) / slots;
+        const long cost = rounds * ((ntile + n - 1) / n + halo);
+        if (best < 0 || cost < best) {
+            best = cost;
+            nseg = n;
+        }
+    }
+    return nseg;
+}
+
 // wide tiling for long filters, narrow for short ones (fewer padded taps)
 bool wide_tiling(int radius) {
     constexpr int from = 24;
@@ -1875,34 +1918,42 @@ bool wide_tiling(int radius) {
 // in while the MFMA route pays a separate epilogue (36 instead of 28 B/pixel of HBM traffic, ~8.3 ms whatever the
 // radius); with the final kernels and the epilogue overlapped by row chunks the MFMA route wins from radius 8
 // (sigma 2 ... 3.75: 8.3-8.4 against 8.7-10.5 ms, the fused kernel being bimodal from box to box; sigma 4: 7.85
-// against 9.26; sigma 7: 8.2 against 9.8) and loses below (sigma 1.1 ... 1.75: 8.3 against 7.65).
+// against 9.26; sigma 7: 8.2 against 9.8) and loses below (sigma 1.1 ... 1.75: 8.3 against 7.65); with both passes in
+// one kernel it wins from radius 4 (sigma 1.25: 6.1 ms against 7.4 for the vector-ALU kernel with the epilogue fused in).
 // Below radius 16 the kernels need more of the caller: the per-column accumulation offset of an axis-0 tile is the
 // sample 16 rows into the (global) 32-row tile, and a row block holds that row for every tile it computes only
-// when it carries 16 ghost rows (17 for the gradient) instead of R (R + 1).  topo_amd_halo_rows asks for them;
+// when it carries 16 ghost rows (17 for the gradient) instead of R (R + 1).  gauss_ghost_rows asks for them;
 // a block that comes with less takes the vector-ALU kernels (mfma_rows_ok), whose results differ from the
 // matrix-core ones in the last bits: row-block bit-identity holds for ghost depths of topo_amd_halo_rows or more
 // (the pre-smoothing of topo.tpi / topo.std included).  The two smooths of an anisotropic gradient keep the
 // radius-16 floor: they have two radii and one ghost depth.
 constexpr int kMfmaSmallFloor = 4;
-int mfma_min_radius_impl(bool for_gradient) {
-    static const int from_gauss = [] {
+constexpr int kNoMfma = 1 << 30;
+int mfma_min_radius() {  // TOPO_AMD_GAUSS_MFMA_MIN_RADIUS
+    static const int r = [] {
         const char* e = std::getenv("TOPO_AMD_GAUSS_MFMA_MIN_RADIUS");
         return std::max(kMfmaSmallFloor, e && *e ? std::atoi(e) : 4);
     }();
-    static const int from_grad = from_gauss;
-    // (round 3: 4, was 8: with both passes in one kernel the route is 6.1 ms at sigma 1.25 on 32768^2, the
-    // vector-ALU kernel with the epilogue fused in 7.4)
-    return for_gradient ? from_grad : from_gauss;
+    return r;
 }
 
-// set by launch_gaussian / launch_gradient for the call: the block's samples are mostly beyond the f16 kernels' range
-// (dem_memo_mostly_large): vector-ALU kernels
-thread_local bool t_no_mfma = false;
-bool mfma_radius(int R, int nx, bool for_gradient = false, bool small_ok = true) {
-    if (t_no_mfma) return false;
-    // (any width from 4 columns: the loaders' 16-byte loads only need dword alignment, which a row of any length has)
-    return R >= std::max(small_ok ? kMfmaSmallFloor : 16, mfma_min_radius_impl(for_gradient)) && R <= 121 && nx >= 4;
+// the raster of the call is a large-sample one: its samples are mostly beyond the f16 kernels' range (a property of the
+// WHOLE raster, common.hpp RasterClass, so that every row block of it takes the same kernels).
+// TOPO_AMD_GAUSS_LARGE_SAMPLE=0: never (A/B: tools/large_raster_time.py)
+bool large_sample_call() {
+    static const bool on = [] {
+        const char* e = std::getenv("TOPO_AMD_GAUSS_LARGE_SAMPLE");
+        return !(e && *e == '0');
+    }();
+    return on && current_class().large;
 }
+
+// the smallest radius a call puts on the matrix cores: none on a large-sample raster (the vector-ALU kernels), from 16
+// where the block has one ghost depth for two radii (!small_ok)
+int mfma_from(bool large, bool small_ok) { return large ? kNoMfma : std::max(small_ok ? kMfmaSmallFloor : 16, mfma_min_radius()); }
+
+// (any width from 4 columns: the loaders' 16-byte loads only need dword alignment, which a row of any length has)
+bool mfma_radius(int R, int nx, int mfma_from) { return R >= mfma_from && R <= 121 && nx >= 4; }
 
 // the accumulation-offset row of every axis-0 tile that holds one of the block's output rows is inside the block
 // (or the block reaches the DEM edge there)
@@ -1914,32 +1965,27 @@ bool mfma_rows_ok(const Block& b, int R) {
     return top && bottom;
 }
 
-int upload_plain_weights(int slot, double sigma, GaussArgs* a) {
-    return upload_weights(slot, sigma, 1, a);  // 2 R + 1 taps, no padding
-}
-
 // ---- f16 route: scales, step count, dispatch over the step count ----
 #ifndef TOPO_F16_NP
 #define TOPO_F16_NP 3  // products per tap block: th h + tm h + th l (4 adds tm l: 7 % slower, same error; lab builds)
 #endif
-int f16_steps(int R);
-thread_local bool t_axis0_one_tile = false;  // set around the two-pass launches queued behind a fused launch
-// two MFMA tiles per offset (MT = 2): axis 1 always; axis 0 from radius 32 (the offset row is 32 rows into a
-// 64-row tile).
-int f16_mt(bool axis1, int R) {
-    if (axis1) return f16_steps(R) < 18 ? 2 : 1;  // the widest window fits LDS 3 times with MT = 2: 2.95 ms against 2.66 with MT = 1
-    // (behind a fused launch - radius 32 ... 47 of the gradient - the two-pass kernels must give the fused kernel's bits,
-    // and its bands are 32-row tiles)
-    if (t_axis0_one_tile) return 1;
-    return R >= 32 ? 2 : 1;
-}
 int f16_steps(int R) { return 2 + (R + 15) / 16 * 2; }  // 16-sample steps of a 32-output tile's window: 32 + 2 Rp, Rp = R rounded up to 16
+
+// The two passes queued behind (or instead of) a fused launch: they run only if *run_if != 0 (nullptr: always), and with
+// one_tile axis 0 keeps the fused kernel's 32-row tiles, so that they give its bits.
+struct TwoPass {
+    const int* run_if = nullptr;
+    bool one_tile = false;
+};
+// two MFMA tiles per offset (MT = 2): axis 1 always; axis 0 from radius 32 (the offset row is 32 rows into a
+// 64-row tile) unless it keeps the fused kernel's tiles (TwoPass::one_tile: radius 32 ... 47 of the gradient)
+int f16_mt(bool axis1, int R, bool one_tile = false) {
+    if (axis1) return f16_steps(R) < 18 ? 2 : 1;  // the widest window fits LDS 3 times with MT = 2: 2.95 ms against 2.66 with MT = 1
+    return R >= 32 && !one_tile ? 2 : 1;
+}
 void set_f16_scales(double sigma, GaussArgs* a) {
-    const int R = gaussian_radius(sigma);
-    double sum = 0.0;
-    for (int k = -R; k <= R; ++k) sum += std::exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
-    const float peak = (float)(1.0 / sum);  // the largest tap, as upload_weights rounds it
-    const int e = 9 - std::ilogb(peak);     // peak 2^e in [512, 1024)
+    const float peak = (float)(1.0 / gauss_taps(sigma));  // the largest tap, as upload_weights rounds it
+    const int e = 9 - std::ilogb(peak);                    // peak 2^e in [512, 1024)
     a->tap_scale = std::ldexp(1.0f, e);
     a->out_scale = std::ldexp(1.0f, 2 - e);  // the data goes in divided by 4
 }
@@ -1971,8 +2017,6 @@ int launch_f16_axis1(long waves, const GaussArgs& a, int rows, int nseg) {
     TOPO_HIP(hipGetLastError());
     return TOPO_AMD_OK;
 }
-// (every band / row block turns its tile order by a number of tiles of its own: profiles/r04_pitch_spread.txt)
-constexpr bool gauss_turn() { return true; }
 // split once (gauss_axis*_s1_kernel): radius 49 ... 121.  TOPO_AMD_GAUSS_SPLIT_ONCE=0: the tile kernels everywhere (A/B)
 bool split_once(int steps) {
     static const bool on = [] {
@@ -2029,22 +2073,18 @@ int launch_f16_axis1_any(int steps, int mt, long waves, const GaussArgs& a, int 
     return TOPO_AMD_EUNSUP;
 }
 
-// set around the two-pass launches that follow a fused launch: they run only if the fused kernel raised its flag
-thread_local const int* t_run_if = nullptr;
-
 // axis 0 on the f16 route: tiles of 32 MT rows on the global grid, one flag byte per 32 x 32 unit
-int run_axis0_f16(const Block& b, GaussArgs a, double sigma) {
+int run_axis0_mfma(const Block& b, double sigma, float* out, int table_slot, const TwoPass& tp = {}) {
     Context& c = ctx();
+    GaussArgs a;
+    TOPO_TRY(gauss_args(b, out, sigma, 1, table_slot, &a));
     set_f16_scales(sigma, &a);
-    a.run_if = t_run_if;
-    a.wild_flag = nullptr;
-    const int mt = f16_mt(false, a.radius), tile = 32 * mt;
+    a.run_if = tp.run_if;
+    const int mt = f16_mt(false, a.radius, tp.one_tile), tile = 32 * mt;
     const int tile_first = b.out_row0 / tile;
     const int ntiles = (b.out_row0 + b.out_rows - 1) / tile - tile_first + 1;
     const int strips = (b.nx + kMfmaCols - 1) / kMfmaCols;
-    // blocks the chip holds at once: the ring of the long filters takes a CU's LDS (one block per CU), two fit up to 80 KB.
-    // (Round 6: this was 2 x the CUs whatever the ring - at radius 49 ... 121 on a 16384-column raster 512 blocks of one per CU:
-    // two rounds, each run restaging its 2 Rp halo rows for half as many tiles.)
+    // blocks the chip holds at once: the ring of the long filters takes a CU's LDS (one block per CU), two fit up to 80 KB
     const size_t ring_bytes = (size_t)(16 * (f16_steps(a.radius) + 2 * (mt - 1))) * kMfmaCols * sizeof(float);
     const int per_cu = ring_bytes <= 80 * 1024 ? 2 : 1;
     int splits = (per_cu * c.num_cu + strips - 1) / strips;
@@ -2070,27 +2110,14 @@ int run_axis1_s1(GaussArgs a, int rows, int nx) {
     Context& c = ctx();
     const int nk = s1_steps(a.radius);
     const int bands = (rows + 15) / 16, ntile = (nx + 31) / 32;
-    // one block of 8 waves per CU: the cut of a band's tiles into runs with the least rounds x (tiles per run + run-in),
-    // runs no shorter than 512 columns
-    const long slots = 8L * c.num_cu;
-    const int halo_tiles = nk;
-    int nseg = 1;
-    long best = -1;
-    for (int n = 1; n <= std::max(1, ntile / 16); ++n) {
-        const long rounds = ((long)bands * n + slots - 1) / slots;
-        const long cost = rounds * ((ntile + n - 1) / n + halo_tiles);
-        if (best < 0 || cost < best) {
-            best = cost;
-            nseg = n;
-        }
-    }
+    // one block of 8 waves per CU; runs no shorter than 512 columns
+    const int nseg = run_cut(bands, ntile, ntile / 16, 8L * c.num_cu, nk);
     const long waves = (long)bands * nseg;
     void* flags = nullptr;
     TOPO_TRY(workspace(10, (size_t)bands * ntile, &flags));
     a.flags = (unsigned char*)flags;
     a.fine_rows = bands;
     a.fine_cols = ntile;
-    a.group0 = gauss_turn() ? 1 : 0;
     TOPO_TRY(launch_s1_axis1_any(nk, waves, a, rows, nseg));
     const int units_a = (rows + 31) / 32, units_b = (nx + 31) / 32;
     const long units = (long)units_a * units_b;
@@ -2100,32 +2127,22 @@ int run_axis1_s1(GaussArgs a, int rows, int nx) {
     return TOPO_AMD_OK;
 }
 
-int run_axis1_f16(GaussArgs a, int rows, int nx, double sigma) {
+// axis 1 on the f16 route: `in` is a plane of `rows` rows; the pass runs only if *run_if != 0 (nullptr: always)
+int run_axis1_mfma(const float* in, int rows, int nx, double sigma, float* out, int table_slot, const int* run_if = nullptr) {
     Context& c = ctx();
+    GaussArgs a;
+    TOPO_TRY(gauss_args(plane_block(in, rows, nx), out, sigma, 1, table_slot, &a));
     set_f16_scales(sigma, &a);
-    a.run_if = t_run_if;
-    a.wild_flag = nullptr;
+    a.run_if = run_if;
+    a.group0 = 1;  // every band turns its tile order by a number of tiles of its own (profiles/r04_pitch_spread.txt)
     const int steps = f16_steps(a.radius);
-    a.group0 = gauss_turn() ? 1 : 0;
     if (split_once(steps)) return run_axis1_s1(a, rows, nx);
     const int mt = f16_mt(true, a.radius);
-    const int nw = steps == 18 && mt == 2 ? 3 : 4;
     const int bands = (rows + 31) / 32;
     const int ntile = (nx + 32 * mt - 1) / (32 * mt), nunit = (nx + 31) / 32;
-    // one block of nw waves per CU (the rings take the LDS): pick the cut of a band's tiles into runs with the least
-    // rounds x (tiles per run + the halo a run restages), runs no shorter than 512 columns
-    const long slots = (long)nw * c.num_cu;
-    const int halo_tiles = (2 * a.radius + 32 * mt - 1) / (32 * mt);
-    int nseg = 1;
-    long best = -1;
-    for (int n = 1; n <= std::max(1, ntile / (16 / mt)); ++n) {
-        const long rounds = ((long)bands * n + slots - 1) / slots;
-        const long cost = rounds * ((ntile + n - 1) / n + halo_tiles);
-        if (best < 0 || cost < best) {
-            best = cost;
-            nseg = n;
-        }
-    }
+    // one block of f16_axis1_waves waves per CU (the rings take the LDS); runs no shorter than 512 columns
+    const int nseg = run_cut(bands, ntile, ntile / (16 / mt), (long)f16_axis1_waves(steps, mt) * c.num_cu,
+                             (2 * a.radius + 32 * mt - 1) / (32 * mt));
     const long waves = (long)bands * nseg;
     const long units = (long)bands * nunit;
     void* flags = nullptr;
@@ -2138,47 +2155,16 @@ int run_axis1_f16(GaussArgs a, int rows, int nx, double sigma) {
     return TOPO_AMD_OK;
 }
 
-int run_axis0_mfma(const Block& b, double sigma, float* out, int table_slot) {
-    GaussArgs a{};
-    TOPO_TRY(upload_plain_weights(table_slot, sigma, &a));
-    a.in = b.in;
-    a.out = out;
-    a.in_rows = b.in_rows;
-    a.in_row0 = b.in_row0;
-    a.gny = b.gny;
-    a.nx = b.nx;
-    a.out_row0 = b.out_row0;
-    a.out_rows = b.out_rows;
-    a.group0 = 0;
-    return run_axis0_f16(b, a, sigma);
-}
-
-int run_axis1_mfma(const float* in, int rows, int nx, double sigma, float* out, int table_slot) {
-    GaussArgs a{};
-    TOPO_TRY(upload_plain_weights(table_slot, sigma, &a));
-    a.in = in;
-    a.out = out;
-    a.in_rows = rows;
-    a.in_row0 = 0;
-    a.gny = rows;
-    a.nx = nx;
-    a.out_row0 = 0;
-    a.out_rows = rows;
-    a.group0 = 0;
-    return run_axis1_f16(a, rows, nx, sigma);
-}
-
 // ---- one kernel for both passes (radius 4 ... 16, one sigma) ----
 bool fused_radius(int R, bool wide_too) {
     static const bool on = [] {
         const char* e = std::getenv("TOPO_AMD_GAUSS_FUSED");
         return !(e && *e == '0');
     }();
-    constexpr int max_r = 47;
     // (the raw blocks and rings of 10 steps no longer fit LDS.)  Radius 32 ... 47 only where the caller says so - the
     // gradient, whose smooth shares HBM with the epilogue (sigma 10: 7.9 -> 6.7 ms); alone the two passes with 64-row
     // tiles on axis 0 are faster there (Gaussian sigma 10: 3.3 ms against 4.4)
-    return on && R >= kMfmaSmallFloor && R <= std::min(wide_too ? 47 : 31, max_r);
+    return on && R >= kMfmaSmallFloor && R <= (wide_too ? 47 : 31);
 }
 template <int S, int CW>
 int launch_fused_f16(dim3 grid, const GaussArgs& a, int tile_first, int ntile_rows, int nseg) {
@@ -2198,19 +2184,9 @@ int launch_fused_f16(dim3 grid, const GaussArgs& a, int tile_first, int ntile_ro
 // (the chunked gradient clears one flag per call and queues the two-pass route behind all of its chunks).
 int run_fused_f16(const Block& b, double sigma, float* out, int table_slot, const int** flag_out) {
     Context& c = ctx();
-    GaussArgs a{};
-    TOPO_TRY(upload_plain_weights(table_slot, sigma, &a));
-    a.in = b.in;
-    a.out = out;
-    a.in_rows = b.in_rows;
-    a.in_row0 = b.in_row0;
-    a.gny = b.gny;
-    a.nx = b.nx;
-    a.out_row0 = b.out_row0;
-    a.out_rows = b.out_rows;
-    a.group0 = gauss_turn() ? 1 : 0;
-    a.flags = nullptr;
-    a.run_if = nullptr;
+    GaussArgs a;
+    TOPO_TRY(gauss_args(b, out, sigma, 1, table_slot, &a));
+    a.group0 = 1;  // (as on axis 1)
     set_f16_scales(sigma, &a);
     if (*flag_out == nullptr) {
         void* flag = nullptr;
@@ -2224,77 +2200,47 @@ int run_fused_f16(const Block& b, double sigma, float* out, int table_slot, cons
     const int ntile_rows = (b.out_row0 + b.out_rows - 1) / 32 - tile_first + 1;
     const int row_blocks = (ntile_rows + 3) / 4;
     const int ntile = (b.nx + 63) / 64;
-    // one block per CU (the LDS): the cut of the columns into runs with the least rounds x (tiles per run + run-in)
-    int nseg = 1;
-    long best = -1;
-    for (int n = 1; n <= std::max(1, ntile / 4); ++n) {
-        const long rounds = ((long)row_blocks * n + c.num_cu - 1) / c.num_cu;
-        const long cost = rounds * ((ntile + n - 1) / n + 1);
-        if (best < 0 || cost < best) {
-            best = cost;
-            nseg = n;
-        }
-    }
+    const int nseg = run_cut(row_blocks, ntile, ntile / 4, c.num_cu, 1);  // one block per CU (the LDS)
     TOPO_TRY(check_grid_rows(row_blocks, "gaussian (fused matrix-core kernel)"));
     const dim3 grid(nseg, row_blocks);
     if (f16_steps(a.radius) == 4) return launch_fused_f16<4, 64>(grid, a, tile_first, ntile_rows, nseg);
     if (f16_steps(a.radius) == 6) return launch_fused_f16<6, 32>(grid, a, tile_first, ntile_rows, nseg);
     return launch_fused_f16<8, 32>(grid, a, tile_first, ntile_rows, nseg);
 }
+// the two passes on the matrix cores: rows `b.out_row0 ...` -> out; tmp: a plane of the same size
+int smooth_two_pass(const Block& b, double sigma, float* tmp, float* out, int table_slot, const TwoPass& tp) {
+    TOPO_TRY(run_axis0_mfma(b, sigma, tmp, table_slot, tp));
+    return run_axis1_mfma(tmp, b.out_rows, b.nx, sigma, out, table_slot + 1, tp.run_if);
+}
 // both passes with one sigma on the matrix cores: rows `b.out_row0 ...` -> out; tmp: a plane of the same size
 // deferred != nullptr (chunked gradient): on the fused route only the fused kernel is launched, raising *deferred (a flag
-// the caller cleared) when it meets a sample that is not a plain finite one; the caller queues smooth_two_pass_if behind
+// the caller cleared) when it meets a sample that is not a plain finite one; the caller queues the two passes behind
 // its last chunk.  Returns whether the two passes are still owed in *owed.
 int smooth_both_mfma(const Block& b, double sigma, float* tmp, float* out, int table_slot, bool for_gradient,
                      const int* deferred = nullptr, bool* owed = nullptr) {
     // (a DEM the fused kernel has met a non-finite or huge sample on - dem_memo, common.hpp - goes straight to the two
     // passes: the fused attempt would only be thrown away again)
-    // (the two passes behind - or instead of - a fused launch keep its tiling of axis 0, hence its bits)
     const bool fused_class = fused_radius(gaussian_radius(sigma), for_gradient);
     const bool fused = fused_class && !dem_memo_wild(b);
     const int* flag = fused ? deferred : nullptr;
     if (fused) TOPO_TRY(run_fused_f16(b, sigma, out, table_slot, &flag));
     if (owed) *owed = fused && deferred != nullptr;
     if (fused && deferred != nullptr) return TOPO_AMD_OK;
-    t_run_if = flag;
-    t_axis0_one_tile = fused_class;
-    int r = run_axis0_mfma(b, sigma, tmp, table_slot);
-    if (r == TOPO_AMD_OK) r = run_axis1_mfma(tmp, b.out_rows, b.nx, sigma, out, table_slot + 1);
-    t_run_if = nullptr;
-    t_axis0_one_tile = false;
-    return r;
-}
-// the two passes over rows `b.out_row0 ...`, run only if *flag != 0 (queued behind fused launches that share the flag)
-int smooth_two_pass_if(const Block& b, double sigma, float* tmp, float* out, int table_slot, const int* flag) {
-    t_run_if = flag;
-    t_axis0_one_tile = true;
-    int r = run_axis0_mfma(b, sigma, tmp, table_slot);
-    if (r == TOPO_AMD_OK) r = run_axis1_mfma(tmp, b.out_rows, b.nx, sigma, out, table_slot + 1);
-    t_run_if = nullptr;
-    t_axis0_one_tile = false;
-    return r;
+    // (the two passes behind - or instead of - a fused launch keep its tiling of axis 0, hence its bits)
+    return smooth_two_pass(b, sigma, tmp, out, table_slot, {flag, fused_class});
 }
 
-int run_axis0(const Block& b, double sigma, float* out, int table_slot, bool mfma_ok = true, bool small_ok = true) {
+int run_axis0(const Block& b, double sigma, float* out, int table_slot, int mfma_from) {
     Context& c = ctx();
-    if (mfma_ok && mfma_radius(gaussian_radius(sigma), b.nx, false, small_ok) && mfma_rows_ok(b, gaussian_radius(sigma)))
-        return run_axis0_mfma(b, sigma, out, table_slot);
-    const bool wide = wide_tiling(gaussian_radius(sigma));
-    GaussArgs a{};
-    TOPO_TRY(upload_weights(table_slot, sigma, wide ? 16 : 8, &a));
-    a.in = b.in;
-    a.out = out;
-    a.in_rows = b.in_rows;
-    a.in_row0 = b.in_row0;
-    a.gny = b.gny;
-    a.nx = b.nx;
-    a.out_row0 = b.out_row0;
-    a.out_rows = b.out_rows;
-    const int tb = wide ? 16 : 8;
+    const int R = gaussian_radius(sigma);
+    if (mfma_radius(R, b.nx, mfma_from) && mfma_rows_ok(b, R)) return run_axis0_mfma(b, sigma, out, table_slot);
+    const int tb = wide_tiling(R) ? 16 : 8;
+    GaussArgs a;
+    TOPO_TRY(gauss_args(b, out, sigma, tb, table_slot, &a));
     a.group0 = b.out_row0 / tb;
     const int groups = (b.out_row0 + b.out_rows - 1) / tb - a.group0 + 1;
     dim3 grid((b.nx + kThreads - 1) / kThreads, groups);
-    if (wide) hipLaunchKernelGGL((gauss_axis0_kernel<16, 16>), grid, dim3(kThreads), 0, c.compute, a);
+    if (tb == 16) hipLaunchKernelGGL((gauss_axis0_kernel<16, 16>), grid, dim3(kThreads), 0, c.compute, a);
     else hipLaunchKernelGGL((gauss_axis0_kernel<8, 8>), grid, dim3(kThreads), 0, c.compute, a);
     TOPO_HIP(hipGetLastError());
     return TOPO_AMD_OK;
@@ -2325,20 +2271,12 @@ int run_axis1_wave_grad(const float* in, int s_row0, int s_rows, double sigma, c
                         float* smooth_out);
 
 // `in` holds exactly the rows [out_row0, out_row0 + out_rows) starting at in_row0 == out_row0
-int run_axis1(const float* in, int rows, int nx, double sigma, float* out, int table_slot, bool small_ok = true) {
-    if (mfma_radius(gaussian_radius(sigma), nx, false, small_ok)) return run_axis1_mfma(in, rows, nx, sigma, out, table_slot);
-    const bool wide = wide_tiling(gaussian_radius(sigma));
-    GaussArgs a{};
-    TOPO_TRY(upload_weights(table_slot, sigma, wide ? 16 : 8, &a));
-    a.in = in;
-    a.out = out;
-    a.in_rows = rows;
-    a.in_row0 = 0;
-    a.gny = rows;
-    a.nx = nx;
-    a.out_row0 = 0;
-    a.out_rows = rows;
-    a.group0 = 0;
+int run_axis1(const float* in, int rows, int nx, double sigma, float* out, int table_slot, int mfma_from) {
+    const int R = gaussian_radius(sigma);
+    if (mfma_radius(R, nx, mfma_from)) return run_axis1_mfma(in, rows, nx, sigma, out, table_slot);
+    const bool wide = wide_tiling(R);
+    GaussArgs a;
+    TOPO_TRY(gauss_args(plane_block(in, rows, nx), out, sigma, wide ? 16 : 8, table_slot, &a));
     if (wide) {
         const int cols_l = 8 * 16 + a.nchunks * 16 - 1;
         if ((size_t)64 * (cols_l | 1) * sizeof(float) > 160 * 1024) {
@@ -2359,8 +2297,7 @@ int run_axis1(const float* in, int rows, int nx, double sigma, float* out, int t
             dim3 g1((nx + 31) / 32, (rows + 31) / 32), g2((rows + 31) / 32, (nx + 31) / 32);
             hipLaunchKernelGGL(transpose_kernel, g1, dim3(kThreads), 0, c.compute, in, (float*)t1, rows, nx);
             TOPO_HIP(hipGetLastError());
-            Block tb{(const float*)t1, nx, 0, nx, rows, 0, nx};
-            TOPO_TRY(run_axis0(tb, sigma, (float*)t2, table_slot));
+            TOPO_TRY(run_axis0(plane_block((const float*)t1, nx, rows), sigma, (float*)t2, table_slot, mfma_from));
             hipLaunchKernelGGL(transpose_kernel, g2, dim3(kThreads), 0, c.compute, (const float*)t2, out, nx, rows);
             TOPO_HIP(hipGetLastError());
             return TOPO_AMD_OK;
@@ -2421,17 +2358,8 @@ int run_axis1_grad(const float* in, int s_row0, int s_rows, int gny, int nx, dou
     // 16-wide tap chunks pay from radius ~60: 4.13 (narrow) / 3.92 ms (wide) at radius 64, 3.33 / 3.65
     // at radius 56 on 16384^2 (tools/gauss_fused_sweep.sh)
     const bool wide = gaussian_radius(sigma) >= wide_from;
-    GaussArgs a{};
-    TOPO_TRY(upload_weights(table_slot, sigma, wide ? 16 : 8, &a));
-    a.in = in;
-    a.out = nullptr;
-    a.in_rows = s_rows;
-    a.in_row0 = s_row0;
-    a.gny = gny;
-    a.nx = nx;
-    a.out_row0 = 0;
-    a.out_rows = 0;
-    a.group0 = 0;
+    GaussArgs a;
+    TOPO_TRY(gauss_args(Block{in, s_rows, s_row0, gny, nx, 0, 0}, nullptr, sigma, wide ? 16 : 8, table_slot, &a));
     if (wide) return launch_axis1_grad<16, 16, 8>(a, g, sigma);
     return launch_axis1_grad<16, 8, 8>(a, g, sigma);
 }
@@ -2449,12 +2377,8 @@ int run_axis1_wave_grad(const float* in, int s_row0, int s_rows, double sigma, c
     // below ~42 of 64 output lanes (radius > 176, sigma > ~44) the transpose path is faster:
     // 11.2 vs 9.0 ms at sigma 50, 68 vs 17 ms at sigma 107 on 16384^2 (tools/gauss_long_crossover.py)
     if (nvl < min_lanes) return TOPO_AMD_EUNSUP;
-    std::vector<double> w(2 * R + 1);
-    double sum = 0.0;
-    for (int k = -R; k <= R; ++k) {
-        w[k + R] = std::exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
-        sum += w[k + R];
-    }
+    std::vector<double> w;
+    const double sum = gauss_taps(sigma, &w);
     // chain step `step` handles lane offset D = d_hi - step: output sub-column t of lane L takes
     // sample s of lane L + D with tap index GC*D + s - t + R
     std::vector<float> wtab((size_t)nsteps * 32, 0.0f), wsum((size_t)nsteps * GC, 0.0f);
@@ -2510,32 +2434,30 @@ int run_axis1_wave_grad(const float* in, int s_row0, int s_rows, double sigma, c
     return TOPO_AMD_OK;
 }
 
-// Full 2-D smooth of rows [row0, row0+rows) into `out`; ws_slot names the scratch plane.
-int smooth_rows(const Block& src, double sigma_y, double sigma_x, int row0, int rows, float* out,
-                int ws_slot, int table_slot, bool small_ok = true) {
+// Full 2-D smooth of rows [row0, row0+rows) into `out`: scratch plane in workspace 0, taps in table slots 1 and 2
+int smooth_rows(const Block& src, double sigma_y, double sigma_x, int row0, int rows, float* out, int mfma_from) {
     Context& c = ctx();
     const bool do_y = sigma_y > 1e-15, do_x = sigma_x > 1e-15;
     Block b = src;
     b.out_row0 = row0;
     b.out_rows = rows;
     const size_t bytes = (size_t)rows * src.nx * sizeof(float);
+    const float* first = src.in + (size_t)(row0 - src.in_row0) * src.nx;
     if (do_y && do_x) {
         void* tmp = nullptr;
-        TOPO_TRY(workspace(ws_slot, bytes, &tmp));
+        TOPO_TRY(workspace(0, bytes, &tmp));
         const int R = gaussian_radius(sigma_y);
-        if (sigma_y == sigma_x && mfma_radius(R, b.nx, false, small_ok) && mfma_rows_ok(b, R)) {
-            TOPO_TRY(smooth_both_mfma(b, sigma_y, (float*)tmp, out, table_slot, false));
+        if (sigma_y == sigma_x && mfma_radius(R, b.nx, mfma_from) && mfma_rows_ok(b, R)) {
+            TOPO_TRY(smooth_both_mfma(b, sigma_y, (float*)tmp, out, 1, false));
         } else {
-            TOPO_TRY(run_axis0(b, sigma_y, (float*)tmp, table_slot, true, small_ok));
-            TOPO_TRY(run_axis1((const float*)tmp, rows, src.nx, sigma_x, out, table_slot + 1, small_ok));
+            TOPO_TRY(run_axis0(b, sigma_y, (float*)tmp, 1, mfma_from));
+            TOPO_TRY(run_axis1((const float*)tmp, rows, src.nx, sigma_x, out, 2, mfma_from));
         }
     } else if (do_y) {
-        TOPO_TRY(run_axis0(b, sigma_y, out, table_slot, true, small_ok));
+        TOPO_TRY(run_axis0(b, sigma_y, out, 1, mfma_from));
     } else if (do_x) {
-        const float* first = src.in + (size_t)(row0 - src.in_row0) * src.nx;
-        TOPO_TRY(run_axis1(first, rows, src.nx, sigma_x, out, table_slot + 1, small_ok));
+        TOPO_TRY(run_axis1(first, rows, src.nx, sigma_x, out, 2, mfma_from));
     } else {
-        const float* first = src.in + (size_t)(row0 - src.in_row0) * src.nx;
         TOPO_HIP(hipMemcpyAsync(out, first, bytes, hipMemcpyDeviceToDevice, c.compute));
     }
     return TOPO_AMD_OK;
@@ -2567,26 +2489,22 @@ int upload_resolution(int res_mode, const void* res_x, const void* res_y, int nx
 
 int gaussian_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
 
-int mfma_min_radius(bool for_gradient) { return mfma_min_radius_impl(for_gradient); }
+int gauss_ghost_rows(double sigma) {
+    const int R = gaussian_radius(sigma);
+    return R >= mfma_min_radius() && R < 16 ? 16 : R;  // (the matrix-core radii below 16: mfma_rows_ok)
+}
 
-// (for the call: the matrix-core routes are closed to a raster whose samples are mostly beyond their range - a property of
-// the WHOLE raster, common.hpp RasterClass, so that every row block of it takes the same kernels)
-struct NoMfmaScope {
-    bool before;
-    explicit NoMfmaScope(const Block&) : before(t_no_mfma) {
-        static const bool on = [] {  // TOPO_AMD_GAUSS_LARGE_SAMPLE=0: never (A/B: tools/large_raster_time.py)
-            const char* e = std::getenv("TOPO_AMD_GAUSS_LARGE_SAMPLE");
-            return !(e && *e == '0');
-        }();
-        if (on && !t_no_mfma) t_no_mfma = current_class().large;
-    }
-    ~NoMfmaScope() { t_no_mfma = before; }
-};
-int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out, bool small_ok) {
-    NoMfmaScope scope(b);
+int gradient_ghost_rows(double sigma, double sig_ratio, bool least) {
+    if (sigma <= 1.0) return 1;
+    if (sig_ratio != 0.0 && sig_ratio != 1.0) return gaussian_radius(std::max(sigma, sigma * sig_ratio)) + 1;
+    return (least ? gaussian_radius(sigma) : gauss_ghost_rows(sigma)) + 1;
+}
+
+int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out) {
+    const int from = mfma_from(large_sample_call(), true);
     for (int r = 0; r < b.out_rows; r += kMaxLaunchRows) {  // (one pass unless the block is taller than a launch covers)
         const int n = std::min(kMaxLaunchRows, b.out_rows - r);
-        TOPO_TRY(smooth_rows(b, sigma_y, sigma_x, b.out_row0 + r, n, out + (size_t)r * b.nx, 0, 1, small_ok));
+        TOPO_TRY(smooth_rows(b, sigma_y, sigma_x, b.out_row0 + r, n, out + (size_t)r * b.nx, from));
     }
     return TOPO_AMD_OK;
 }
@@ -2628,12 +2546,183 @@ Block smoothed_rows_block(const Block& b) {
     r.out_rows = s1 - r.out_row0;
     return r;
 }
+
+// the stand-alone epilogue, `rows` grid rows from g.out_row0 on `stream`: four pixels a thread on rows of 8 columns or more,
+// one below; run_if != nullptr: the kernels that return at once unless *run_if != 0 (and stride over g's rows)
+int launch_epilogue(GradArgs g, int rows, hipStream_t stream, const int* run_if = nullptr) {
+    g.run_if = run_if;
+    const bool wide = g.nx >= 8;
+    const dim3 grid(((wide ? (g.nx + 3) / 4 : g.nx) + kThreads - 1) / kThreads, rows);
+    if (wide && run_if) hipLaunchKernelGGL(gradient_epilogue4_if_kernel, grid, dim3(kThreads), 0, stream, g);
+    else if (wide) hipLaunchKernelGGL(gradient_epilogue4_kernel, grid, dim3(kThreads), 0, stream, g);
+    else if (run_if) hipLaunchKernelGGL(gradient_epilogue_if_kernel, grid, dim3(kThreads), 0, stream, g);
+    else hipLaunchKernelGGL(gradient_epilogue_kernel, grid, dim3(kThreads), 0, stream, g);
+    TOPO_HIP(hipGetLastError());
+    return TOPO_AMD_OK;
+}
+
+// Sobel: sigma <= 1 (topo.py:628-629).  One sigma (topo.py:630-631) on the matrix cores: chunked from
+// TOPO_AMD_GRAD_CHUNK_MIN_ROWS output rows, else in one shot; elsewhere the vector-ALU kernels with axis 1 and the
+// epilogue fused.  Two sigmas (topo.py:633-635): two smooths.
+enum class GradRoute { Sobel, Chunked, Mfma, Valu, Aniso };
+GradRoute gradient_route(const Block& b, double sigma, double sig_ratio, int mfma_from) {
+    static const int chunk_min = [] {
+        const char* e = std::getenv("TOPO_AMD_GRAD_CHUNK_MIN_ROWS");
+        return e && *e ? std::atoi(e) : 2048;  // (the interior of a 4096-row shard of the 8-GPU split goes in two chunks)
+    }();
+    if (sigma <= 1.0) return GradRoute::Sobel;
+    if (sig_ratio != 1.0) return GradRoute::Aniso;
+    const int R = gaussian_radius(sigma);
+    if (!mfma_radius(R, b.nx, mfma_from) || !mfma_rows_ok(smoothed_rows_block(b), R)) return GradRoute::Valu;
+    return b.out_rows >= chunk_min ? GradRoute::Chunked : GradRoute::Mfma;
+}
+
+// The chunked matrix-core route: the smooth is MFMA-bound and leaves HBM idle, the epilogue is HBM-bound and needs no
+// LDS, so the rows go in chunks and the epilogue of chunk k runs on a second stream next to the smooth of chunk k + 1
+// (15.7 -> 14.5 ms at sigma 30.25 on 32768^2 with 4 -> 8 chunks; one chunk: 18.5).  Row chunks are row blocks: same bits.
+int gradient_chunked(const Block& b, double sigma, const GradArgs& g) {
+    Context& c = ctx();
+    static const int NCH = [] {
+        const char* e = std::getenv("TOPO_AMD_GRAD_CHUNKS");
+        return std::max(1, std::min(64, e && *e ? std::atoi(e) : 8));
+    }();
+    static const int chunk_rows = [] {  // smallest chunk (rows); a chunk's planes should fit the 256 MB Infinity Cache
+        const char* e = std::getenv("TOPO_AMD_GRAD_CHUNK_ROWS");
+        // 32768^2, chunks x rows (profiles/r03_gradient_chunks.txt): 8 x 4096 8.04 / 13.70 ms at sigma 3.25 / 30.25,
+        // 16 x 2048 7.77 / 13.50, 32 x 1024 8.27 / 14.55, 64 x 512 8.54 / 16.16
+        // with the f16 kernels (profiles/r03_gauss_f16.txt, section 7): 4 x 8192 6.15 / 9.01, 8 x 4096 6.08 / 9.12,
+        // 12 x 2752 6.31 / 9.40, 16 x 2048 6.31 / 9.59, 32 x 1024 6.64 / 11.20; one stream: 6.71 / 10.43
+        return std::max(256, e && *e ? std::atoi(e) : 4096);
+    }();
+    const int R = gaussian_radius(sigma);
+    const bool gated = c.ghost.armed;
+    // A short block (a row shard: 4096 rows) in few chunks leaves the smooth of its first chunk and the epilogue of its
+    // last one uncovered: the fused route (one kernel per chunk, nothing restaged across a cut but Rp rows) goes in at
+    // least 6 chunks of 512 rows or more, the two-pass route (every chunk restages 2 R rows on axis 0: 24 % at
+    // radius 121 and 1024 rows) in at least 3.  One 4096-row shard in loop-back, sigma 3.25 / 30.25, ms per step
+    // (profiles/r04_shard_fused.txt): 2 chunks 0.98 / 1.56, 3: 0.95 / 1.55, 4: 0.83 / 1.60, 6: 0.81 / 1.73, 8: 0.85 / 1.91.
+    const int min_chunks = std::max(2, std::min(fused_radius(R, true) ? 6 : 3, b.out_rows / 512));
+    if (!c.aux) {
+        TOPO_HIP(hipStreamCreateWithFlags(&c.aux, hipStreamNonBlocking));
+        for (auto& e : c.aux_ready) TOPO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        TOPO_HIP(hipEventCreateWithFlags(&c.aux_done, hipEventDisableTiming));
+    }
+    // smoothed rows [s0, s1), cut at global multiples of 32 rows (the row tiles of the axis-0 kernel; a chunk of 32 k
+    // rows is also a whole number of axis-1 bands).  Behind the smooth of a chunk, the epilogue emits the output rows
+    // whose two neighbour rows are smoothed by then: the chunk's own rows, short of the first / last one where the chunk
+    // next to it is still to come, plus the row that chunk left behind where it is done.
+    const Block sb = smoothed_rows_block(b);
+    const int s0 = sb.out_row0, s1 = sb.out_row0 + sb.out_rows;
+    const int out_end = b.out_row0 + b.out_rows;
+    const size_t bytes = (size_t)(s1 - s0) * b.nx * sizeof(float);
+    void *pa = nullptr, *pb = nullptr;
+    TOPO_TRY(workspace(1, bytes, &pa));
+    TOPO_TRY(workspace(2, bytes, &pb));
+    // chunks of >= 2048 rows (every chunk restages the 2 R halo rows of the axis-0 ring: 12 % at radius 121); a
+    // short block (a row shard) goes in at least min_chunks, because the epilogue of its LAST chunk runs alone
+    const int nch = std::max(min_chunks, std::min(NCH, (s1 - s0) / chunk_rows));
+    const int per = std::max(32, ((s1 - s0 + nch - 1) / nch + 31) / 32 * 32);
+    struct Chunk {
+        int c0, c1;
+        bool ghost, done;
+    };
+    std::vector<Chunk> chunks;
+    // Taper (from 4 chunks): the smooth of the chunk processed FIRST and the epilogue of the one processed LAST run
+    // uncovered, so those two chunks are a quarter of the others (>= 256 rows).  Processing order = row order, except in
+    // a row shard, where the first chunk processed is the second in row order (the top one waits for the exchange).
+    // (32768^2, sigma 3.25: 5.76 -> 5.52 ms; a 4096-row shard in 6 chunks LOSES 7 % with a 256-row first chunk, so only
+    // blocks whose chunks are 2048 rows and more are tapered; sigma 30.25: no difference either way)
+    const bool taper = nch >= 4 && (s1 - s0) / nch >= 2048;
+    const int small = std::max(256, ((s1 - s0) / nch / 4 + 31) / 32 * 32);
+    const int big = taper ? std::max(32, ((s1 - s0 - 2 * small + nch - 3) / (nch - 2) + 31) / 32 * 32) : per;
+    const int first_small = gated ? 1 : 0;  // row-order index of the chunk processed first
+    for (int c0 = s0, k = 0; c0 < s1; ++k) {
+        const int want = taper && k == first_small ? small : big;
+        int c1 = (c0 + want) / 32 * 32;
+        if (taper && s1 - c1 < small + 32 && s1 - c1 > 0 && c1 < s1) c1 = std::max(c0 + 32, (s1 - small) / 32 * 32);  // leave the small last chunk
+        if (c1 + 32 > s1 || c1 <= c0) c1 = s1;  // no sliver at the end
+        // row shard with its exchange in flight: does the filter of these rows reach into the ghost rows?
+        chunks.push_back({c0, c1, gated && (c0 - R < c.ghost.ghost_lo || c1 + R > c.ghost.ghost_hi), false});
+        c0 = c1;
+    }
+    TOPO_REQUIRE(chunks.size() <= 64, "gradient: %zu row chunks (at most 64)", chunks.size());
+    // Row shard: the chunks that stay clear of the ghost rows go first, on the rows the shard owns (the ghost rows are
+    // being written meanwhile; staging clamps to the view), then the compute stream waits for the exchange and the
+    // chunks at the two seams follow on the whole block - ordinary chunks of the ordinary pipeline, no seam strips
+    // of their own, and the exchange hides behind the first chunks.  Row chunks are row blocks: same bits.
+    std::vector<int> order;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int k = 0; k < (int)chunks.size(); ++k)
+            if (chunks[k].ghost == (pass == 1)) order.push_back(k);
+    Block owned = b;
+    if (gated) {
+        const int lo = std::max(b.in_row0, c.ghost.ghost_lo), hi = std::min(b.in_row0 + b.in_rows, c.ghost.ghost_hi);
+        owned.in = b.in + (size_t)(lo - b.in_row0) * b.nx;
+        owned.in_row0 = lo;
+        owned.in_rows = hi - lo;
+        c.ghost.armed = false;  // taken
+    }
+    // one "met a sample that is not a plain finite one" flag for the call: the fused kernels of all chunks raise it, and
+    // the two-pass route (five launches that return at once on an ordinary DEM) is queued ONCE, behind the last
+    // chunk, over all rows - not behind every chunk, where its launches sat in front of the next chunk's smooth
+    void* wild = nullptr;
+    TOPO_TRY(workspace(11, 64, &wild));
+    TOPO_HIP(hipMemsetAsync(wild, 0, sizeof(int), c.compute));
+    GradArgs sg = g;  // the epilogue over the smoothed plane
+    sg.gx_src = sg.gy_src = (const float*)pb;
+    sg.s_row0 = s0;
+    sg.s_rows = s1 - s0;
+    bool owed = false;
+    bool waited = !gated;
+    for (int k : order) {
+        Chunk& ck = chunks[k];
+        if (ck.ghost && !waited) {
+            TOPO_TRY(topo_amd_halo_wait());
+            waited = true;
+        }
+        Block rows = ck.ghost || !gated ? b : owned;
+        rows.out_row0 = ck.c0;
+        rows.out_rows = ck.c1 - ck.c0;
+        float* a_k = (float*)pa + (size_t)(ck.c0 - s0) * b.nx;
+        float* b_k = (float*)pb + (size_t)(ck.c0 - s0) * b.nx;
+        bool owes = false;
+        TOPO_TRY(smooth_both_mfma(rows, sigma, a_k, b_k, 1, true, (const int*)wild, &owes));
+        owed = owed || owes;
+        ck.done = true;
+        TOPO_HIP(hipEventRecord(c.aux_ready[k], c.compute));
+        TOPO_HIP(hipStreamWaitEvent(c.aux, c.aux_ready[k], 0));
+        const bool first = k == 0, last = k + 1 == (int)chunks.size();
+        const int o0 = std::max(b.out_row0, first ? b.out_row0 : (chunks[k - 1].done ? ck.c0 - 1 : ck.c0 + 1));
+        const int o1 = std::min(out_end, last ? out_end : (chunks[k + 1].done ? ck.c1 + 1 : ck.c1 - 1));
+        if (o1 > o0) {
+            GradArgs gk = sg;
+            const size_t shift = (size_t)(o0 - b.out_row0) * b.nx;
+            gk.out_row0 = o0;
+            gk.out_rows = o1 - o0;
+            gk.dx = g.dx ? g.dx + shift : nullptr;
+            gk.dy = g.dy ? g.dy + shift : nullptr;
+            gk.slope = g.slope ? g.slope + shift : nullptr;
+            gk.aspect = g.aspect ? g.aspect + shift : nullptr;
+            if (g.res_mode == TOPO_AMD_RES_2D) {
+                gk.res_x = g.res_x + shift;
+                gk.res_y = g.res_y + shift;
+            }
+            TOPO_TRY(launch_epilogue(gk, o1 - o0, c.aux));
+        }
+    }
+    if (!waited) TOPO_TRY(topo_amd_halo_wait());
+    TOPO_HIP(hipEventRecord(c.aux_done, c.aux));
+    TOPO_HIP(hipStreamWaitEvent(c.compute, c.aux_done, 0));
+    if (!owed) return TOPO_AMD_OK;
+    // behind every chunk and its epilogue: smooth [s0, s1) again by the two passes and redo the epilogue, if the flag is up
+    TOPO_TRY(smooth_two_pass(sb, sigma, (float*)pa, (float*)pb, 1, {(const int*)wild, true}));
+    return launch_epilogue(sg, std::min(b.out_rows, 512), c.compute, (const int*)wild);
+}
 }  // namespace
 
 int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode,
                     const void* res_x, const void* res_y, float* dx, float* dy, float* slope,
                     float* aspect) {
-    NoMfmaScope scope(b);
     if (b.out_rows > kMaxLaunchRows) {
         if (ctx().ghost.armed) return TOPO_AMD_EUNSUP;
         for (int r = 0; r < b.out_rows; r += kMaxLaunchRows) {
@@ -2654,16 +2743,11 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
     Context& c = ctx();
     TOPO_REQUIRE(res_mode >= 0 && res_mode <= 2, "gradient: bad res_mode %d", res_mode);
     TOPO_REQUIRE(res_x && res_y, "gradient: resolution arrays are NULL");
-    // a row shard whose exchange is in flight (common.hpp, GhostGate): only the chunked matrix-core route below knows
-    // what to do with it; every other route says so before it launches anything
-    static const int chunk_min = [] {
-        const char* e = std::getenv("TOPO_AMD_GRAD_CHUNK_MIN_ROWS");
-        return e && *e ? std::atoi(e) : 2048;  // (the interior of a 4096-row shard of the 8-GPU split goes in two chunks)
-    }();
-    const bool gated = c.ghost.armed;
-    if (gated && !(sigma > 1.0 && sig_ratio == 1.0 && mfma_radius(gaussian_radius(sigma), b.nx, true) &&
-                   mfma_rows_ok(smoothed_rows_block(b), gaussian_radius(sigma)) && b.out_rows >= chunk_min))
-        return TOPO_AMD_EUNSUP;
+    const bool large = large_sample_call();
+    const GradRoute route = gradient_route(b, sigma, sig_ratio, mfma_from(large, true));
+    // a row shard whose exchange is in flight (common.hpp, GhostGate): only the chunked route knows what to do with it;
+    // every other route says so before it launches anything
+    if (c.ghost.armed && route != GradRoute::Chunked) return TOPO_AMD_EUNSUP;
     GradArgs g{};
     TOPO_TRY(upload_resolution(res_mode, res_x, res_y, b.nx, b.gny, &g.res_x, &g.res_y));
     g.res_mode = res_mode;
@@ -2676,257 +2760,57 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
     g.slope = slope;
     g.aspect = aspect;
     TOPO_TRY(check_grid_rows(b.out_rows, "sobel / gradient epilogue"));
-    dim3 grid((b.nx + kThreads - 1) / kThreads, b.out_rows);
-    if (sigma <= 1.0) {  // topo.py:628-629
+    if (route == GradRoute::Sobel) {
         g.raw = b.in;
         g.raw_rows = b.in_rows;
         g.raw_row0 = b.in_row0;
-        hipLaunchKernelGGL(sobel_kernel<true>, grid, dim3(kThreads), 0, c.compute, g);
+        hipLaunchKernelGGL(sobel_kernel<true>, dim3((b.nx + kThreads - 1) / kThreads, b.out_rows), dim3(kThreads), 0, c.compute, g);
         TOPO_HIP(hipGetLastError());
         return TOPO_AMD_OK;
     }
     TOPO_REQUIRE(b.gny >= 2 && b.nx >= 2,
                  "gradient: numpy.gradient needs at least 2 samples per axis (got %d x %d)",
                  b.gny, b.nx);
-    // Matrix-core route on a large block: the smooth is MFMA-bound and leaves HBM idle, the epilogue is
-    // HBM-bound and needs no LDS, so the rows go in chunks and the epilogue of chunk k runs on a second stream
-    // next to the smooth of chunk k + 1 (15.7 -> 14.5 ms at sigma 30.25 on 32768^2 with 4 -> 8 chunks; one chunk:
-    // 18.5).  Row chunks are row blocks:
-    // same bits.
-    if (sigma > 1.0 && sig_ratio == 1.0 && mfma_radius(gaussian_radius(sigma), b.nx, true) &&
-        mfma_rows_ok(smoothed_rows_block(b), gaussian_radius(sigma)) && b.out_rows >= chunk_min) {
-        // (widths that are not multiples of 4, or planes that are not 16-byte aligned: the one-pixel-per-thread epilogue)
-        const bool wide_epilogue = b.nx >= 8;
-        static const int NCH = [] {
-            const char* e = std::getenv("TOPO_AMD_GRAD_CHUNKS");
-            return std::max(1, std::min(64, e && *e ? std::atoi(e) : 8));
-        }();
-        static const int chunk_rows = [] {  // smallest chunk (rows); a chunk's planes should fit the 256 MB Infinity Cache
-            const char* e = std::getenv("TOPO_AMD_GRAD_CHUNK_ROWS");
-            // 32768^2, chunks x rows (profiles/r03_gradient_chunks.txt): 8 x 4096 8.04 / 13.70 ms at sigma 3.25 / 30.25,
-            // 16 x 2048 7.77 / 13.50, 32 x 1024 8.27 / 14.55, 64 x 512 8.54 / 16.16
-            // with the f16 kernels (profiles/r03_gauss_f16.txt, section 7): 4 x 8192 6.15 / 9.01, 8 x 4096 6.08 / 9.12,
-            // 12 x 2752 6.31 / 9.40, 16 x 2048 6.31 / 9.59, 32 x 1024 6.64 / 11.20; one stream: 6.71 / 10.43
-            return std::max(256, e && *e ? std::atoi(e) : 4096);
-        }();
-        constexpr bool use_aux = true;
-        // A short block (a row shard: 4096 rows) in few chunks leaves the smooth of its first chunk and the epilogue of its
-        // last one uncovered: the fused route (one kernel per chunk, nothing restaged across a cut but Rp rows) goes in at
-        // least 6 chunks of 512 rows or more, the two-pass route (every chunk restages 2 R rows on axis 0: 24 % at
-        // radius 121 and 1024 rows) in at least 3.  One 4096-row shard in loop-back, sigma 3.25 / 30.25, ms per step
-        // (profiles/r04_shard_fused.txt): 2 chunks 0.98 / 1.56, 3: 0.95 / 1.55, 4: 0.83 / 1.60, 6: 0.81 / 1.73, 8: 0.85 / 1.91.
-        constexpr int kMinChunksEnv = 0;
-        const int kMinChunks = kMinChunksEnv ? kMinChunksEnv
-                                             : std::max(2, std::min(fused_radius(gaussian_radius(sigma), true) ? 6 : 3, b.out_rows / 512));
-        if (!c.aux) {
-            TOPO_HIP(hipStreamCreateWithFlags(&c.aux, hipStreamNonBlocking));
-            for (auto& e : c.aux_ready) TOPO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            TOPO_HIP(hipEventCreateWithFlags(&c.aux_done, hipEventDisableTiming));
-        }
-        // smoothed rows [s0, s1) = the output rows plus one neighbour row inside the DEM, cut at global multiples
-        // of 32 rows (the row tiles of the axis-0 kernel; a chunk of 32 k rows is also a whole number of axis-1
-        // bands).  Behind the smooth of a chunk, the epilogue emits the output rows whose two neighbour rows are smoothed
-        // by then: the chunk's own rows, short of the first / last one where the chunk next to it is still to come,
-        // plus the row that chunk left behind where it is done.
-        const int s0 = b.out_row0 > 0 ? b.out_row0 - 1 : 0;
-        const int s1 = (b.out_row0 + b.out_rows + 1 < b.gny) ? b.out_row0 + b.out_rows + 1 : b.gny;
-        const int out_end = b.out_row0 + b.out_rows;
-        const size_t bytes = (size_t)(s1 - s0) * b.nx * sizeof(float);
-        void *pa = nullptr, *pb = nullptr;
-        TOPO_TRY(workspace(1, bytes, &pa));
-        TOPO_TRY(workspace(2, bytes, &pb));
-        // chunks of >= 2048 rows (every chunk restages the 2 R halo rows of the axis-0 ring: 12 % at radius 121); a
-        // short block (a row shard) goes in at least kMinChunks, because the epilogue of its LAST chunk runs alone
-        const int nch = std::max(kMinChunks, std::min(NCH, (s1 - s0) / chunk_rows));
-        const int per = std::max(32, ((s1 - s0 + nch - 1) / nch + 31) / 32 * 32);
-        struct Chunk {
-            int c0, c1;
-            bool ghost, done;
-        };
-        std::vector<Chunk> chunks;
-        const int R = gaussian_radius(sigma);
-        // Taper (TOPO_AMD_GRAD_TAPER, default on from 4 chunks): the smooth of the chunk processed FIRST and the epilogue of
-        // the one processed LAST run uncovered, so those two chunks are a quarter of the others (>= 256 rows).  Processing
-        // order = row order, except in a row shard, where the first chunk processed is the second in row order (the top
-        // one waits for the exchange).
-        constexpr bool taper_on = true;
-        // (32768^2, sigma 3.25: 5.76 -> 5.52 ms; a 4096-row shard in 6 chunks LOSES 7 % with a 256-row first chunk, so only
-        // blocks whose chunks are 2048 rows and more are tapered; sigma 30.25: no difference either way)
-        const bool taper = taper_on && nch >= 4 && (s1 - s0) / nch >= 2048;
-        const int small = std::max(256, ((s1 - s0) / nch / 4 + 31) / 32 * 32);
-        const int big = taper ? std::max(32, ((s1 - s0 - 2 * small + nch - 3) / (nch - 2) + 31) / 32 * 32) : per;
-        const int first_small = gated ? 1 : 0;  // row-order index of the chunk processed first
-        for (int c0 = s0, k = 0; c0 < s1; ++k) {
-            const int want = taper && k == first_small ? small : big;
-            int c1 = (c0 + want) / 32 * 32;
-            if (taper && s1 - c1 < small + 32 && s1 - c1 > 0 && c1 < s1) c1 = std::max(c0 + 32, (s1 - small) / 32 * 32);  // leave the small last chunk
-            if (c1 + 32 > s1 || c1 <= c0) c1 = s1;  // no sliver at the end
-            // row shard with its exchange in flight: does the filter of these rows reach into the ghost rows?
-            chunks.push_back({c0, c1, gated && (c0 - R < c.ghost.ghost_lo || c1 + R > c.ghost.ghost_hi), false});
-            c0 = c1;
-        }
-        TOPO_REQUIRE(chunks.size() <= 64, "gradient: %zu row chunks (at most 64)", chunks.size());
-        // Row shard: the chunks that stay clear of the ghost rows go first, on the rows the shard owns (the ghost rows are
-        // being written meanwhile; staging clamps to the view), then the compute stream waits for the exchange and the
-        // chunks at the two seams follow on the whole block - ordinary chunks of the ordinary pipeline, no seam strips
-        // of their own, and the exchange hides behind the first chunks.  Row chunks are row blocks: same bits.
-        std::vector<int> order;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int k = 0; k < (int)chunks.size(); ++k)
-                if (chunks[k].ghost == (pass == 1)) order.push_back(k);
-        Block owned = b;
-        if (gated) {
-            const int lo = std::max(b.in_row0, c.ghost.ghost_lo), hi = std::min(b.in_row0 + b.in_rows, c.ghost.ghost_hi);
-            owned.in = b.in + (size_t)(lo - b.in_row0) * b.nx;
-            owned.in_row0 = lo;
-            owned.in_rows = hi - lo;
-            c.ghost.armed = false;  // taken
-        }
-        // one "met a sample that is not a plain finite one" flag for the call: the fused kernels of all chunks raise it, and
-        // the two-pass route (five launches that return at once on an ordinary DEM) is queued ONCE, behind the last
-        // chunk, over all rows - not behind every chunk, where its launches sat in front of the next chunk's smooth
-        void* wild = nullptr;
-        TOPO_TRY(workspace(11, 64, &wild));
-        TOPO_HIP(hipMemsetAsync(wild, 0, sizeof(int), c.compute));
-        bool owed = false;
-        bool waited = !gated;
-        for (int k : order) {
-            Chunk& ck = chunks[k];
-            if (ck.ghost && !waited) {
-                TOPO_TRY(topo_amd_halo_wait());
-                waited = true;
-            }
-            Block rows = ck.ghost || !gated ? b : owned;
-            rows.out_row0 = ck.c0;
-            rows.out_rows = ck.c1 - ck.c0;
-            float* a_k = (float*)pa + (size_t)(ck.c0 - s0) * b.nx;
-            float* b_k = (float*)pb + (size_t)(ck.c0 - s0) * b.nx;
-            bool owes = false;
-            TOPO_TRY(smooth_both_mfma(rows, sigma, a_k, b_k, 1, true, (const int*)wild, &owes));
-            owed = owed || owes;
-            ck.done = true;
-            if (use_aux) {
-                TOPO_HIP(hipEventRecord(c.aux_ready[k], c.compute));
-                TOPO_HIP(hipStreamWaitEvent(c.aux, c.aux_ready[k], 0));
-            }
-            const bool first = k == 0, last = k + 1 == (int)chunks.size();
-            const int o0 = std::max(b.out_row0, first ? b.out_row0 : (chunks[k - 1].done ? ck.c0 - 1 : ck.c0 + 1));
-            const int o1 = std::min(out_end, last ? out_end : (chunks[k + 1].done ? ck.c1 + 1 : ck.c1 - 1));
-            if (o1 > o0) {
-                GradArgs gk = g;
-                const size_t shift = (size_t)(o0 - b.out_row0) * b.nx;
-                gk.out_row0 = o0;
-                gk.out_rows = o1 - o0;
-                gk.dx = dx ? dx + shift : nullptr;
-                gk.dy = dy ? dy + shift : nullptr;
-                gk.slope = slope ? slope + shift : nullptr;
-                gk.aspect = aspect ? aspect + shift : nullptr;
-                if (res_mode == TOPO_AMD_RES_2D) {
-                    gk.res_x = g.res_x + shift;
-                    gk.res_y = g.res_y + shift;
-                }
-                gk.gx_src = (const float*)pb;
-                gk.gy_src = (const float*)pb;
-                gk.s_row0 = s0;
-                gk.s_rows = s1 - s0;
-                TOPO_TRY(check_grid_rows(o1 - o0, "gradient epilogue"));
-                if (wide_epilogue) {
-                    dim3 grid4(((b.nx + 3) / 4 + kThreads - 1) / kThreads, o1 - o0);
-                    hipLaunchKernelGGL(gradient_epilogue4_kernel, grid4, dim3(kThreads), 0, use_aux ? c.aux : c.compute, gk);
-                } else {
-                    dim3 grid1((b.nx + kThreads - 1) / kThreads, o1 - o0);
-                    hipLaunchKernelGGL(gradient_epilogue_kernel, grid1, dim3(kThreads), 0, use_aux ? c.aux : c.compute, gk);
-                }
-                TOPO_HIP(hipGetLastError());
-            }
-        }
-        if (!waited) TOPO_TRY(topo_amd_halo_wait());
-        if (owed) {
-            // behind every chunk and its epilogue: smooth [s0, s1) again by the two passes and redo the epilogue, if the flag is up
-            if (use_aux) {
-                TOPO_HIP(hipEventRecord(c.aux_done, c.aux));
-                TOPO_HIP(hipStreamWaitEvent(c.compute, c.aux_done, 0));
-            }
-            Block rows = b;
-            rows.out_row0 = s0;
-            rows.out_rows = s1 - s0;
-            TOPO_TRY(smooth_two_pass_if(rows, sigma, (float*)pa, (float*)pb, 1, (const int*)wild));
-            GradArgs gk = g;
-            gk.gx_src = (const float*)pb;
-            gk.gy_src = (const float*)pb;
-            gk.s_row0 = s0;
-            gk.s_rows = s1 - s0;
-            gk.run_if = (const int*)wild;
-            const int if_rows = std::min(b.out_rows, 512);
-            if (wide_epilogue) {
-                dim3 grid4(((b.nx + 3) / 4 + kThreads - 1) / kThreads, if_rows);
-                hipLaunchKernelGGL(gradient_epilogue4_if_kernel, grid4, dim3(kThreads), 0, c.compute, gk);
-            } else {
-                dim3 grid1((b.nx + kThreads - 1) / kThreads, if_rows);
-                hipLaunchKernelGGL(gradient_epilogue_if_kernel, grid1, dim3(kThreads), 0, c.compute, gk);
-            }
-            TOPO_HIP(hipGetLastError());
-            return TOPO_AMD_OK;
-        }
-        if (use_aux) {
-            TOPO_HIP(hipEventRecord(c.aux_done, c.aux));
-            TOPO_HIP(hipStreamWaitEvent(c.compute, c.aux_done, 0));
-        }
-        return TOPO_AMD_OK;
-    }
-    // smoothed rows needed: the output rows plus one neighbour row inside the DEM
-    const int s0 = b.out_row0 > 0 ? b.out_row0 - 1 : 0;
-    const int s1 = (b.out_row0 + b.out_rows + 1 < b.gny) ? b.out_row0 + b.out_rows + 1 : b.gny;
-    const int s_rows = s1 - s0;
-    const size_t bytes = (size_t)s_rows * b.nx * sizeof(float);
+    if (route == GradRoute::Chunked) return gradient_chunked(b, sigma, g);
+    const Block s = smoothed_rows_block(b);
+    const size_t bytes = (size_t)s.out_rows * b.nx * sizeof(float);
     void *plane_a = nullptr, *plane_b = nullptr;
     TOPO_TRY(workspace(1, bytes, &plane_a));
-    if (sig_ratio == 1.0) {  // topo.py:630-631: one smooth; axis 1 and the epilogue run fused
-        Block rows = b;
-        rows.out_row0 = s0;
-        rows.out_rows = s_rows;
-        const bool mfma = mfma_radius(gaussian_radius(sigma), b.nx, true) && mfma_rows_ok(rows, gaussian_radius(sigma));
-        if (!mfma) TOPO_TRY(run_axis0(rows, sigma, (float*)plane_a, 1, false));
+    if (route == GradRoute::Valu) {
+        TOPO_TRY(run_axis0(s, sigma, (float*)plane_a, 1, kNoMfma));
         // short and medium filters: LDS-tiled axis 1 (9.8 vs 13.6 ms at sigma 3.25 on 32768^2); long
         // filters: wave-shift axis 1 (26.7 vs 27.8 ms at sigma 30.25) while enough lanes produce output
         constexpr int fused_max = 92;
         // the LDS-tiled fused kernel while its tile fits (320 columns: radius 92), the wave-shift one
         // beyond: 2.67 vs 3.63 ms at radius 32, 3.33 vs 4.07 at 56, 4.60 vs 5.17 at 92 on 16384^2
-        if (!mfma) {
-            if (gaussian_radius(sigma) <= fused_max) {
-                const int r = run_axis1_grad((const float*)plane_a, s0, s_rows, b.gny, b.nx, sigma, g, 2);
-                if (r != TOPO_AMD_EUNSUP) return r;
-            }
-            const int r = run_axis1_wave_grad((const float*)plane_a, s0, s_rows, sigma, g, nullptr);
+        if (gaussian_radius(sigma) <= fused_max) {
+            const int r = run_axis1_grad((const float*)plane_a, s.out_row0, s.out_rows, b.gny, b.nx, sigma, g, 2);
             if (r != TOPO_AMD_EUNSUP) return r;
         }
-        // matrix-core range: the smooth of the chunked route above (same kernels, same bits), then the stand-alone
-        // epilogue; a filter wider than a wavefront can chain: finish the smooth unfused (beyond radius 121 axis 1 goes
-        // through the wave-shift or the transpose path)
+        const int r = run_axis1_wave_grad((const float*)plane_a, s.out_row0, s.out_rows, sigma, g, nullptr);
+        if (r != TOPO_AMD_EUNSUP) return r;
+        // a filter wider than a wavefront can chain: finish the smooth unfused (beyond radius 121 axis 1 goes through
+        // the wave-shift or the transpose path)
         TOPO_TRY(workspace(2, bytes, &plane_b));
-        if (mfma) TOPO_TRY(smooth_both_mfma(rows, sigma, (float*)plane_a, (float*)plane_b, 1, true));
-        else TOPO_TRY(run_axis1((const float*)plane_a, s_rows, b.nx, sigma, (float*)plane_b, 2));
+        TOPO_TRY(run_axis1((const float*)plane_a, s.out_rows, b.nx, sigma, (float*)plane_b, 2, mfma_from(large, true)));
         plane_a = plane_b;
-    } else {  // topo.py:633-635
+    } else if (route == GradRoute::Mfma) {  // the smooth of the chunked route (same kernels, same bits)
+        TOPO_TRY(workspace(2, bytes, &plane_b));
+        TOPO_TRY(smooth_both_mfma(s, sigma, (float*)plane_a, (float*)plane_b, 1, true));
+        plane_a = plane_b;
+    } else {
         const double perp = sigma * sig_ratio;
         TOPO_TRY(workspace(2, bytes, &plane_b));
         // (two radii, one ghost depth: the matrix-core kernels only from radius 16, where they need no more
         // ghost rows than the filter itself)
-        TOPO_TRY(smooth_rows(b, perp, sigma, s0, s_rows, (float*)plane_a, 0, 1, /*small_ok=*/false));
-        TOPO_TRY(smooth_rows(b, sigma, perp, s0, s_rows, (float*)plane_b, 0, 1, /*small_ok=*/false));
+        TOPO_TRY(smooth_rows(b, perp, sigma, s.out_row0, s.out_rows, (float*)plane_a, mfma_from(large, false)));
+        TOPO_TRY(smooth_rows(b, sigma, perp, s.out_row0, s.out_rows, (float*)plane_b, mfma_from(large, false)));
     }
     g.gx_src = (const float*)plane_a;
     g.gy_src = (const float*)plane_b;
-    g.s_row0 = s0;
-    g.s_rows = s_rows;
-    if (b.nx >= 8) {
-        dim3 grid4(((b.nx + 3) / 4 + kThreads - 1) / kThreads, b.out_rows);
-        hipLaunchKernelGGL(gradient_epilogue4_kernel, grid4, dim3(kThreads), 0, c.compute, g);
-    } else {
-        hipLaunchKernelGGL(gradient_epilogue_kernel, grid, dim3(kThreads), 0, c.compute, g);
-    }
-    TOPO_HIP(hipGetLastError());
-    return TOPO_AMD_OK;
+    g.s_row0 = s.out_row0;
+    g.s_rows = s.out_rows;
+    return launch_epilogue(g, b.out_rows, c.compute);
 }
 
 }  // namespace topo
