@@ -277,6 +277,22 @@ int topo_amd_valley_route(int* route);
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);
 
+/* Gaps of a DEM filled with the nearest valid sample along x: replaces hlp.fill_na(dem_ds) (reference helpers.py:137-154,
+ * interpolate_na(dim="x", method="nearest", fill_value="extrapolate")) together with the masking at or below
+ * CFG.min_elevation of get_dem_netcdf (helpers.py:30-31).  A sample is MISSING when it is NaN or, with a threshold
+ * (min_elevation not NaN), when !(x > (float)min_elevation) in float32; +-inf and -0.0 are otherwise valid and copied bit for
+ * bit.  Per row, a missing sample takes the valid sample L or R on either side with the smaller coordinate when
+ * x[j] <= x_lo / 2 + x_hi / 2 (float64; scipy's interp1d "nearest", a tie goes to the smaller coordinate), the edge sample
+ * beyond the first / last valid one.  A row with fewer than two valid samples is left alone: without a threshold its NaNs
+ * keep their bits, with one every missing sample of it becomes 0x7FC00000 (numpy's NaN, as np.where(x > m, x, nan) writes).
+ * x_coords: HOST double[nx], finite and strictly monotonic (either direction), or NULL for the column index; anything else
+ * is TOPO_AMD_EINVAL.  out may be the block's own output rows (in place: only missing samples are written, only valid
+ * ones read); missing_out (uint8 [out_rows x nx], 1 = missing before the fill) may be NULL.  Rows are independent: no
+ * ghost rows, a row shard fills its own rows with this call.  Writing the rows drops the raster class remembered or
+ * declared for them (above).                                                                                           */
+int topo_amd_fill_na_dev(const float* in, int in_rows, int in_row0, int gny, int nx, const double* x_coords,
+                         double min_elevation, int out_row0, int out_rows, float* out, uint8_t* missing_out);
+
 /* ---- descriptors, host-buffer form (single block, whole DEM) -------------------------- */
 /* Upload, kernels and download run in row chunks on three streams (upload || kernels || download: row blocks give the
  * single block's bits), page-locked arrays (topo_amd_host_alloc) and pageable ones alike.  The device planes a call needs
@@ -304,6 +320,9 @@ int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, c
 int topo_amd_gauss_f32(const float* dem, int ny, int nx, double sigma_y, double sigma_x,
                        float* out);
 int topo_amd_sobel_f32(const float* dem, int ny, int nx, float* dx_out, float* dy_out);
+/* topo_amd_fill_na_dev on a host array (pipelined like the others; out may be dem; missing_out: uint8 [ny x nx] or NULL). */
+int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coords, double min_elevation, float* out,
+                         uint8_t* missing_out);
 /* res_mode RES_2D here takes HOST float arrays [ny x nx].                                 */
 int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double sig_ratio,
                           int res_mode, const void* res_x, const void* res_y, float* dx_out,

@@ -68,6 +68,8 @@ SIGNATURES = {
     "topo_amd_valley_ridge_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int,
                                             C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp]),
     "topo_amd_mean_std_dev": (C.c_int, [_vp, C.c_size_t, _f64p, _f64p]),
+    "topo_amd_fill_na_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_double, C.c_int, C.c_int,
+                                       _vp, _vp]),
     "topo_amd_valley_ridge_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int,
                                             C.c_double, C.c_double, _vp, _vp]),
     "topo_amd_tpi_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
@@ -76,6 +78,7 @@ SIGNATURES = {
     "topo_amd_tpi_std_multi_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _vp, _vp]),
     "topo_amd_gauss_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
     "topo_amd_sobel_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "topo_amd_fill_na_f32": (C.c_int, [_vp, C.c_int, C.c_int, _f64p, C.c_double, _vp, _vp]),
     "topo_amd_gradient_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                         _vp, _vp, _vp, _vp, _vp, _vp]),
     "topo_amd_sx_f32": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _f64p, C.c_int, C.c_int,

@@ -397,7 +397,7 @@ struct TableSlot {
     std::vector<char> last;
     hipEvent_t copied = nullptr;
 };
-TableSlot g_slots[6];
+TableSlot g_slots[kTables];
 }  // namespace
 
 int upload_table(int slot, const void* host, size_t bytes, void** out) {
@@ -603,8 +603,11 @@ int download(void* host, const void* dev, size_t bytes) {
 // TOPO_AMD_HOST_DOWNLOADS=thread / inline: who issues the downloads (default: by the arrays, below).  All three are read at
 // every call (a getenv each), so a test can walk through them in one process.
 struct HostPlane {
-    float* host;
-    float* dev;
+    void* host;
+    void* dev;
+    size_t elem = sizeof(float);  // bytes per sample (the missing mask of topo_amd_fill_na_f32: 1)
+    void* host_row(int r, int nx) const { return (char*)host + (size_t)r * nx * elem; }
+    const void* dev_row(int r, int nx) const { return (const char*)dev + (size_t)r * nx * elem; }
 };
 int pipeline_chunk_rows(int ny, int nx) {
     const char* e = std::getenv("TOPO_AMD_HOST_PIPELINE");
@@ -645,7 +648,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
         const int rc = compute(ny, 0, ny);
         if (rc != TOPO_AMD_OK && rc != TOPO_AMD_EEMPTY) return rc;
         run.ready();
-        for (const HostPlane& o : outs) TOPO_TRY(download(o.host, o.dev, (size_t)ny * row_bytes));
+        for (const HostPlane& o : outs) TOPO_TRY(download(o.host, o.dev, (size_t)ny * nx * o.elem));
         TOPO_HIP(hipStreamSynchronize(c.compute));
         return rc;
     }
@@ -702,7 +705,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
             hipError_t e = hipStreamWaitEvent(c.down, computed[j], 0);
             for (size_t k = 0; k < outs.size() && e == hipSuccess; ++k)
                 if (outs[k].host)
-                    e = hipMemcpyAsync(outs[k].host + (size_t)r0 * nx, outs[k].dev + (size_t)r0 * nx, (size_t)(r1 - r0) * row_bytes,
+                    e = hipMemcpyAsync(outs[k].host_row(r0, nx), outs[k].dev_row(r0, nx), (size_t)(r1 - r0) * nx * outs[k].elem,
                                        hipMemcpyDeviceToHost, c.down);
             if (e != hipSuccess) {
                 down_rc = TOPO_AMD_EHIP;
@@ -757,7 +760,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
                 hipError_t e = hipStreamWaitEvent(c.down, computed[next], 0);
                 for (size_t q = 0; q < outs.size() && e == hipSuccess; ++q)
                     if (outs[q].host)
-                        e = hipMemcpyAsync(outs[q].host + (size_t)r0 * nx, outs[q].dev + (size_t)r0 * nx, (size_t)(r1 - r0) * row_bytes,
+                        e = hipMemcpyAsync(outs[q].host_row(r0, nx), outs[q].dev_row(r0, nx), (size_t)(r1 - r0) * nx * outs[q].elem,
                                            hipMemcpyDeviceToHost, c.down);
                 if (e != hipSuccess) {
                     set_error("download of a row chunk failed: %s", hipGetErrorString(e));
@@ -890,9 +893,9 @@ int topo_amd_shutdown(void) {
         g_declared.clear();
     }
     valley_fft_release();  // FFT plans hold the stream that goes away below
-    for (int i = 0; i < 12; ++i)
+    for (int i = 0; i < kWorkspaces; ++i)
         if (c.ws[i]) (void)hipFree(c.ws[i]);
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < kTables; ++i) {
         if (c.tab[i]) (void)hipFree(c.tab[i]);
         if (g_slots[i].pinned) (void)hipHostFree(g_slots[i].pinned);
         if (g_slots[i].copied) (void)hipEventDestroy(g_slots[i].copied);
@@ -1450,6 +1453,45 @@ int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* s
     return launch_mean_std(in, count, mean, stdev);
 }
 
+// ---- gap filling: nearest valid sample along x (fill.hip; reference helpers.py:137-154 and :30-31) ---------------------
+namespace {
+// x_coords (host, nx entries; NULL: the column index) must be finite and strictly monotonic; *ascending: their direction
+int check_fill_coords(const double* x, int nx, bool* ascending) {
+    *ascending = true;
+    if (!x) return TOPO_AMD_OK;
+    for (int i = 0; i < nx; ++i) TOPO_REQUIRE(std::isfinite(x[i]), "fill_na: x_coords[%d] is not finite", i);
+    if (nx >= 2) *ascending = x[1] > x[0];
+    for (int i = 1; i < nx; ++i)
+        TOPO_REQUIRE(*ascending ? x[i] > x[i - 1] : x[i] < x[i - 1], "fill_na: x_coords are not strictly monotonic at index %d", i);
+    return TOPO_AMD_OK;
+}
+}  // namespace
+
+int topo_amd_fill_na_dev(const float* in, int in_rows, int in_row0, int gny, int nx, const double* x_coords, double min_elevation,
+                         int out_row0, int out_rows, float* out, uint8_t* missing_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(out != nullptr, "fill_na: NULL output");
+    Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
+    TOPO_TRY(check_block(b, 0, 0, "fill_na"));
+    bool ascending = true;
+    TOPO_TRY(check_fill_coords(x_coords, nx, &ascending));
+    // in place means the block's own output rows; any other output must lie apart from them
+    const size_t bytes = (size_t)out_rows * nx * sizeof(float);
+    const uintptr_t own = (uintptr_t)(in + (size_t)(out_row0 - in_row0) * nx), o = (uintptr_t)out;
+    TOPO_REQUIRE(o == own || o + bytes <= own || own + bytes <= o, "fill_na: the output overlaps the input rows without being them");
+    const double* d_x = nullptr;
+    if (x_coords) {
+        void* t = nullptr;
+        TOPO_TRY(upload_table(6, x_coords, (size_t)nx * sizeof(double), &t));
+        d_x = (const double*)t;
+    }
+    forget_plane(out, out_rows, nx);  // (in place: what was remembered or declared for the DEM's rows goes with them)
+    if (missing_out) dem_memo_forget(missing_out, (size_t)out_rows * nx);
+    const bool thresh = !std::isnan(min_elevation);
+    return launch_fill_na(b, d_x, ascending, thresh, thresh ? (float)min_elevation : 0.0f, out, missing_out);
+}
+
 // ---- host-buffer entry points ----------------------------------------------------------------
 int topo_amd_tpi_std_f32(const float* dem, int ny, int nx, int size, double sigma, float* tpi_out,
                          float* std_out) {
@@ -1563,6 +1605,28 @@ int topo_amd_sobel_f32(const float* dem, int ny, int nx, float* dx_out, float* d
                          [&](int view_rows, int r0, int rows) {
                              return topo_amd_sobel_dev((const float*)d_in, view_rows, 0, ny, nx, r0, rows, shift((float*)d_dx, r0, nx),
                                                        shift((float*)d_dy, r0, nx));
+                         });
+}
+
+int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coords, double min_elevation, float* out,
+                         uint8_t* missing_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(dem && out && ny >= 1 && nx >= 1, "fill_na: bad arguments");
+    bool ascending = true;
+    TOPO_TRY(check_fill_coords(x_coords, nx, &ascending));  // (before anything moves)
+    const size_t bytes = (size_t)ny * nx * sizeof(float), mask_bytes = (size_t)ny * nx;
+    HostRun run;
+    void *d_plane = nullptr, *d_miss = nullptr;
+    TOPO_TRY(run.alloc(&d_plane, bytes));  // filled in place on the device
+    if (missing_out) TOPO_TRY(run.alloc(&d_miss, mask_bytes));
+    run.prefault(out, bytes);
+    run.prefault(missing_out, mask_bytes);
+    return run_pipelined(run, dem, (float*)d_plane, ny, nx, 0, 0, true, {{out, d_plane}, {missing_out, d_miss, 1}},
+                         [&](int view_rows, int r0, int rows) {
+                             return topo_amd_fill_na_dev((const float*)d_plane, view_rows, 0, ny, nx, x_coords, min_elevation, r0, rows,
+                                                         shift((float*)d_plane, r0, nx),
+                                                         d_miss ? (uint8_t*)d_miss + (size_t)r0 * nx : nullptr);
                          });
 }
 

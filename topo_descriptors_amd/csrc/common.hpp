@@ -87,6 +87,8 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
+constexpr int kWorkspaces = 13;  // Context::ws slots (12: the fill's wide-row words)
+constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;
     int device = -1;
@@ -124,11 +126,11 @@ struct Context {
     hipEvent_t input_ready = nullptr;  // compute -> comm dependency
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // grow-only device workspaces (never freed between calls: no hipMalloc in the hot path)
-    void* ws[12] = {};
-    size_t ws_bytes[12] = {};
-    // small parameter tables (disc runs, gaussian taps, sx offsets, resolutions)
-    void* tab[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t tab_bytes[6] = {0, 0, 0, 0, 0, 0};
+    void* ws[kWorkspaces] = {};
+    size_t ws_bytes[kWorkspaces] = {};
+    // small parameter tables (disc runs, gaussian taps, sx offsets, resolutions, fill coordinates)
+    void* tab[kTables] = {};
+    size_t tab_bytes[kTables] = {};
 };
 
 Context& ctx();
@@ -207,6 +209,9 @@ int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double
 int launch_sx_multi(const Block& b, int n_az, const int32_t* first, const int32_t* dj, const int32_t* di,
                     const double* dist, const int32_t* window, double height, float* const* outs);
 int launch_synth(float* out, int rows, int row0, int nx, uint32_t seed, bool integer_valued);
+// nearest valid sample along x (fill.hip): output rows [out_row0, out_row0 + out_rows) of the block; xs: device double[nx]
+// (nullptr: the column index); out may be the block's own rows (in place); missing: uint8 plane or nullptr
+int launch_fill_na(const Block& b, const double* xs, bool ascending, bool use_thresh, float thresh, float* out, uint8_t* missing);
 // valley / ridge index (valley.hip): taps = per angle ksize^2 x 4 floats (plane sums, flipped)
 // the same by FFT, for kernels of any size (valley_fft.hip)
 int launch_valley_ridge_fft(const Block& b, const float* taps, const int32_t* ksize, const float* angles,

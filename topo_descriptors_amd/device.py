@@ -12,11 +12,14 @@ from . import _lib
 
 
 class DeviceArray:
-    """rows x nx float32 plane in HBM owned by libtopo_amd."""
+    """rows x nx plane in HBM owned by libtopo_amd: float32, or uint8 for the missing mask of :meth:`Block.fill_na`."""
 
-    def __init__(self, rows, nx):
+    def __init__(self, rows, nx, dtype=np.float32):
         self.rows, self.nx = int(rows), int(nx)
-        self.nbytes = self.rows * self.nx * 4
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"DeviceArray: float32 or uint8 planes, not {self.dtype}")
+        self.nbytes = self.rows * self.nx * self.dtype.itemsize
         p = C.c_void_p()
         _lib.check(_lib.lib().topo_amd_malloc(C.byref(p), self.nbytes), "topo_amd_malloc")
         self.ptr = p.value
@@ -29,17 +32,17 @@ class DeviceArray:
         return d
 
     def row_ptr(self, row):
-        return self.ptr + int(row) * self.nx * 4
+        return self.ptr + int(row) * self.nx * self.dtype.itemsize
 
     def to_host(self, row0=0, rows=None):
         rows = self.rows - row0 if rows is None else rows
-        out = np.empty((rows, self.nx), dtype=np.float32)
+        out = np.empty((rows, self.nx), dtype=self.dtype)
         _lib.check(_lib.lib().topo_amd_memcpy_d2h(_lib.ptr(out), self.row_ptr(row0), out.nbytes),
                    "memcpy_d2h")
         return out
 
     def upload_rows(self, array, row0=0):
-        a = _lib.as_f32(array)
+        a = np.ascontiguousarray(array, dtype=self.dtype)
         _lib.check(_lib.lib().topo_amd_memcpy_h2d(self.row_ptr(row0), _lib.ptr(a), a.nbytes),
                    "memcpy_h2d")
 
@@ -271,6 +274,24 @@ class Block:
             *self._head(), taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p),
             angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes), float(mean), float(stdev), o0, on,
             norm.ptr, direction.ptr), "valley_ridge_dev")
+
+
+    def fill_na(self, out, missing=None, x_coords=None, min_elevation=None, out_row0=None, out_rows=None):
+        """Missing samples (NaN, or at or below ``min_elevation``) of the output rows replaced by the nearest valid sample
+        along x (``topo_amd_fill_na_dev``; ``helpers.fill_na_gpu`` for the rules).  ``out``: a float32 DeviceArray holding
+        the output rows from its first row, or this block's own plane (in place); ``missing``: a uint8 DeviceArray of the
+        output rows (1 = missing before the fill) or None; ``x_coords``: one coordinate per column or None (the index)."""
+        from .helpers import _fill_coords  # noqa: PLC0415
+
+        o0, on = self._range(out_row0, out_rows)
+        x = _fill_coords(x_coords, self.nx)
+        if missing is not None and missing.dtype != np.uint8:
+            raise ValueError("Block.fill_na: the missing mask is a uint8 DeviceArray")
+        dst = self.data.row_ptr(self.first + o0 - self.row0) if out is self.data else out.ptr
+        m = np.nan if min_elevation is None else float(min_elevation)
+        _lib.check(_lib.lib().topo_amd_fill_na_dev(*self._head(), None if x is None else x.ctypes.data_as(_lib._f64p), m,
+                                                   o0, on, dst, missing.ptr if missing is not None else None),
+                   "fill_na_dev")
 
 
 def mean_std(array):

@@ -216,6 +216,44 @@ def fill_na_array(values, x_coords=None):
     return out
 
 
+def _fill_coords(x_coords, nx):
+    """``x_coords`` as the C ABI takes them (float64, contiguous; None stays None), refused unless finite, strictly
+    monotonic and one per column - before any library call."""
+    if x_coords is None:
+        return None
+    x = np.ascontiguousarray(np.asarray(x_coords, dtype=np.float64).ravel())
+    if x.size != nx:
+        raise ValueError(f"fill_na: {x.size} x_coords for {nx} columns")
+    if not np.isfinite(x).all():
+        raise ValueError("fill_na: x_coords must be finite")
+    step = np.diff(x)
+    if not ((step > 0).all() or (step < 0).all()):
+        raise ValueError("fill_na: x_coords must be strictly monotonic (increasing or decreasing)")
+    return x
+
+
+def fill_na_gpu(values, x_coords=None, min_elevation=None):
+    """``(missing, filled)``: what the reference's ``fill_na`` returns as ``(ind_nans, filled)`` (helpers.py:137-154),
+    computed on the GPU (``topo_amd_fill_na_f32``) with the bits of :func:`fill_na_array`.  A sample is missing when it is
+    NaN or, with ``min_elevation``, at or below it (float32 comparison: the masking of ``get_dem_netcdf``, helpers.py:30-31);
+    each is replaced by the nearest valid sample along x (``x_coords``, or the column index), rows with fewer than two
+    valid samples are left alone.  ``missing`` is a boolean array: ``np.nonzero(missing)`` is the reference's ``ind_nans``,
+    and the mask itself works as ``ind_nans`` in ``batch.compute_*``.  A DataArray-like input is re-wrapped."""
+    from . import _lib, topo  # noqa: PLC0415  (topo imports this module)
+
+    a, rewrap = topo._unwrap(values)
+    topo._check_2d(a, "fill_na_gpu")
+    x = _fill_coords(x_coords, a.shape[1])
+    src = _lib.as_f32(a)
+    out = np.empty_like(src)
+    missing = np.empty(src.shape, dtype=np.uint8)
+    m = np.nan if min_elevation is None else float(min_elevation)
+    _lib.check(_lib.lib().topo_amd_fill_na_f32(_lib.ptr(src), src.shape[0], src.shape[1],
+                                               None if x is None else x.ctypes.data_as(_lib._f64p), m, _lib.ptr(out),
+                                               _lib.ptr(missing)), "topo_amd_fill_na_f32")
+    return missing.view(np.bool_), rewrap(out)
+
+
 def fill_na(dem_ds):
     """``(ind_nans, filled Dataset)``: where the DEM has NaNs, and the DEM with them interpolated
     along x by the nearest valid value (reference helpers.py:137-154).  Needs xarray."""
