@@ -158,7 +158,7 @@ int topo_amd_disc_tap_count(int size);
 int topo_amd_disc_mask(int size, float* mask);
 /* Ghost rows a row block needs above / below its output rows for one descriptor.
  * p0: size (TPI/STD) | sigma (GAUSS: of axis 0; GRADIENT: the `sigma` argument of the gradient)
- * p1: pre-smoothing sigma (TPI/STD, 0 = none) | sig_ratio (GRADIENT; 0 or 1 = isotropic) | unused
+ * p1: pre-smoothing sigma (TPI/STD/VALLEY_RIDGE, 0 = none) | sig_ratio (GRADIENT; 0 or 1 = isotropic) | unused
  * GRADIENT answers exactly the depth topo_amd_shard_gradient(sigma, sig_ratio) lays its block out with.
  * For SX pass the extremes of the offset table instead: p0 = -min(dj), p1 = max(dj).
  * For Gaussian radii int(4 sigma + 0.5) of 4 ... 15 (the gradient's too; also the pre-smoothing of TPI / STD) the
@@ -412,6 +412,46 @@ int topo_amd_shard_sx_multi(float* block, int rows_local, int row0, int gny, int
 int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx,
                                 const float* taps, const int32_t* ksize, const float* angles,
                                 int n_angles, int n_planes, float* norm_out, float* dir_out);
+
+/* ---- the smoothed descriptors and the gap fill on a row shard ------------------------------------------------------------
+ * The Gaussian (topo.dem), the pre-smoothed TPI / STD and valley / ridge index (topo.py:172-173, :297-298, :424-427) and
+ * fill_na (helpers.py:137-154), each with the single GPU's bits on the shard's rows (the valley: given the same moments).
+ * Every call is collective like the ones above: all ranks make it, in the same order, with the same parameters.
+ *
+ * Smoothed descriptors: ONE exchange of raw ghost rows, of depth disc / valley reach + gauss_ghost rows (topo_amd_halo_rows
+ * of TPI / STD with p1 = sigma, of VALLEY_RIDGE with p1 = sigma).  The shard smooths every row its disc / kernels will read
+ * into a plane of the library's workspace - the rows that need only owned raw rows while the exchange is in flight, the two
+ * seam bands behind its event - and runs ONE descriptor launch over its owned rows from that plane (its "ghost rows" were
+ * smoothed locally: no second exchange, no gate).
+ * Raster class: the Gaussian takes the class of the WHOLE raw raster (declared collectively, as every shard call does), so
+ * no shard picks the vector-ALU or the matrix-core kernels from its own rows.  The smoothed field is a raster of its own:
+ * as the single GPU's Block(smooth) scans the whole smoothed plane, TPI / STD classify the OWNED smoothed rows of all ranks
+ * together (topo_amd_shard_classify: an all-reduce at every call) before the disc launch, so two shardings of a DEM take the
+ * same disc kernels.  The valley kernels are chosen by the kernel tables alone, never by the class: no scan there.      */
+/* topo.dem on a shard: reflect at global rows 0 and gny - 1 only, 4 sigma truncation, the single call's NaN footprint
+ * (as far as any row block with this ghost depth has it: the vector-ALU kernels also carry a non-finite sample through zero
+ * taps up to 30 rows past the filter, which a block reads only where it holds the rows).
+ * Ghost depth topo_amd_halo_rows(GAUSS, sigma_y); out: rows_local x nx.                                                 */
+int topo_amd_shard_gaussian(float* block, int rows_local, int row0, int gny, int nx, double sigma_y, double sigma_x,
+                            float* out);
+/* ndimage.gaussian_filter(dem, sigma) then TPI / STD of size (either output may be NULL).  Ghost depth
+ * topo_amd_halo_rows(TPI, size, sigma).  sigma <= 0: exactly topo_amd_shard_tpi_std.                                    */
+int topo_amd_shard_tpi_std_smoothed(float* block, int rows_local, int row0, int gny, int nx, int size, double sigma,
+                                    float* tpi_out, float* std_out);
+/* topo_amd_shard_valley_ridge on the field smoothed with sigma.  Ghost depth topo_amd_halo_rows(VALLEY_RIDGE, largest
+ * kernel side, sigma).  The mean and standard deviation are float64 moments of the OWNED SMOOTHED rows, all-reduced;
+ * moments_out (host double[2], or NULL) receives the (mean, std) the call standardised with.  sigma <= 0: the result of
+ * topo_amd_shard_valley_ridge (and its moments).                                                                         */
+int topo_amd_shard_valley_ridge_smoothed(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
+                                         const int32_t* ksize, const float* angles, int n_angles, int n_planes,
+                                         double sigma, float* norm_out, float* dir_out, double* moments_out);
+/* topo_amd_fill_na_dev on the owned rows: row-local, no exchange, no RCCL call.  out may be the owned rows themselves (in
+ * place); missing (uint8 rows_local x nx) may be NULL; x_coords: the WHOLE DEM's, one per column.  An in-place fill drops
+ * the raster class declared for the rows it writes, and the next shard call re-classifies - collectively.  So this call is
+ * collective by contract: all ranks or none, or the ranks' declared state drifts apart and the next call hangs in the
+ * all-reduce one rank skips.                                                                                             */
+int topo_amd_shard_fill_na(float* block, int rows_local, int row0, int gny, int nx, const double* x_coords,
+                           double min_elevation, float* out, uint8_t* missing);
 
 #ifdef __cplusplus
 }

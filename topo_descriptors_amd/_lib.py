@@ -104,6 +104,12 @@ SIGNATURES = {
                                           C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "topo_amd_shard_sx": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_double, _vp]),
+    "topo_amd_shard_gaussian": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
+    "topo_amd_shard_tpi_std_smoothed": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp,
+                                                  _vp]),
+    "topo_amd_shard_valley_ridge_smoothed": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp,
+                                                       C.c_int, C.c_int, C.c_double, _vp, _vp, _f64p]),
+    "topo_amd_shard_fill_na": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_double, _vp, _vp]),
 }
 
 UNIQUE_ID_BYTES = 128

@@ -1290,6 +1290,9 @@ int topo_amd_halo_rows(int descriptor, double p0, double p1, int* above, int* be
             const int32_t kmax = (int32_t)p0;
             TOPO_REQUIRE(kmax >= 1, "halo_rows: kernel side %d", kmax);
             (void)valley_ridge_reach(&kmax, 1, above, below);
+            const int R = p1 > 0.0 ? gauss_ghost_rows(p1) : 0;  // the pre-smoothing (topo_amd_shard_valley_ridge_smoothed)
+            *above += R;
+            *below += R;
             return TOPO_AMD_OK;
         }
         default:
@@ -2318,23 +2321,15 @@ int topo_amd_shard_sx_multi(float* block, int rows_local, int row0, int gny, int
     });
 }
 
-int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
-                                const int32_t* ksize, const float* angles, int n_angles, int n_planes,
-                                float* norm_out, float* dir_out) {
-    TOPO_ENTER();
-    TOPO_TRY(require_ready());
-    TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1,
-                 "shard_valley_ridge: NULL argument");
-    int above = 0, below = 0;
-    (void)valley_ridge_reach(ksize, n_angles, &above, &below);
-    TOPO_TRY(shard_view(&block, above, below, "shard_valley_ridge"));
-    block += shard_view_offset(above, nx);
-    // the standardisation needs the mean and standard deviation of the WHOLE DEM (topo.py:427):
-    // float64 moments about 0 of the owned rows, then the one all-reduce of the whole path.
-    // On a DEM of whole metres the three numbers are exact integers (< 2^53), so every sharding
-    // gets the same mean and std.
+}  // extern "C"
+
+namespace {
+// The mean and standard deviation of the WHOLE DEM (topo.py:427) from the rows this rank owns: float64 moments about 0,
+// then the one all-reduce of the path.  On a DEM of whole metres the three numbers are exact integers (< 2^53), so every
+// sharding gets the same mean and std.
+int shard_moments(const float* owned, int rows_local, int nx, double* mean, double* stdev) {
     double mom[3] = {(double)rows_local * (double)nx, 0.0, 0.0};
-    TOPO_TRY(launch_moments(block + (size_t)above * nx, (size_t)rows_local * nx, 0.0, false, &mom[1], &mom[2]));
+    TOPO_TRY(launch_moments(owned, (size_t)rows_local * nx, 0.0, false, &mom[1], &mom[2]));
     if (g_comm.size > 1) {
         void* d_mom = nullptr;
         TOPO_TRY(workspace(0, 3 * sizeof(double), &d_mom));
@@ -2343,10 +2338,27 @@ int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny,
         TOPO_HIP(hipMemcpyAsync(mom, d_mom, sizeof(mom), hipMemcpyDeviceToHost, ctx().compute));
         TOPO_HIP(hipStreamSynchronize(ctx().compute));
     }
-    const double mean = mom[1] / mom[0];
-    double var = mom[2] / mom[0] - mean * mean;
+    *mean = mom[1] / mom[0];
+    double var = mom[2] / mom[0] - *mean * *mean;
     if (var < 0.0) var = 0.0;
-    const double stdev = std::sqrt(var);
+    *stdev = std::sqrt(var);
+    return TOPO_AMD_OK;
+}
+
+int shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx, const float* taps, const int32_t* ksize,
+                       const float* angles, int n_angles, int n_planes, float* norm_out, float* dir_out, double* moments_out) {
+    TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1,
+                 "shard_valley_ridge: NULL argument");
+    int above = 0, below = 0;
+    (void)valley_ridge_reach(ksize, n_angles, &above, &below);
+    TOPO_TRY(shard_view(&block, above, below, "shard_valley_ridge"));
+    block += shard_view_offset(above, nx);
+    double mean = 0.0, stdev = 0.0;
+    TOPO_TRY(shard_moments(block + (size_t)above * nx, rows_local, nx, &mean, &stdev));
+    if (moments_out) {
+        moments_out[0] = mean;
+        moments_out[1] = stdev;
+    }
     Shard s = make_shard(block, rows_local, row0, gny, nx, above, below);
     return run_overlapped(block, s, above, below, [&](const Block& view, int o0, int on) {
         Block b = view;
@@ -2356,6 +2368,189 @@ int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny,
         return launch_valley_ridge(b, taps, ksize, angles, n_angles, n_planes, mean, stdev,
                                    shift(norm_out, o0 - row0, nx), shift(dir_out, o0 - row0, nx));
     });
+}
+
+// Gaussian of rows [s0, s1) of a shard into `plane` (row s0 first), around ONE ghost-row exchange of depth above / below
+// that this starts: the rows whose filter (g ghost rows: gauss_ghost_rows) stays inside the owned rows first, on the owned
+// rows, while the exchange is in flight; then the compute stream waits for the exchange's event and the two seam bands
+// follow on the block with its ghost rows.  Row blocks of the Gaussian carrying g ghost rows give the single block's bits.
+// The owned-row part keeps kGaussSeamSlack rows more away from the seams: the vector-ALU axis-0 kernel (radii below 4, and
+// every radius on a raster of the large-sample class) fetches whole row groups of up to 16 rows with taps in chunks of
+// up to 16, so a launch reads up to R + 30 rows beyond its output rows, with zero taps; a non-finite sample there still
+// makes the output NaN (0 x NaN).  In the single call those rows are the DEM's; on the owned rows alone they would be
+// clamped to the last owned row - another NaN footprint.  The seam bands read them on the block with its ghost rows, as
+// any row block with g ghost rows does.
+// (This is run_three's order.  run_gated would hand the launcher the whole shard with the gate armed, and only the
+// gradient's chunked pipeline knows what to do with that: launch_gaussian has no row chunks of its own to put the seam
+// ones last, so it would answer EUNSUP and the call would take run_three anyway.)
+int smooth_shard_rows(float* block, const Shard& s, int above, int below, double sigma_y, double sigma_x, int g, int s0,
+                      int s1, float* plane) {
+    const int nx = s.whole.nx, end = s.row0 + s.rows_local;
+    Shard band = s;  // the exchange, the views and the clean-up of run_three, over the rows [s0, s1)
+    band.row0 = s0;
+    band.rows_local = s1 - s0;
+    constexpr int kGaussSeamSlack = 32;
+    band.interior0 = std::min(s1, std::max(s0, s.row0 > 0 ? s.row0 + g + kGaussSeamSlack : s.row0));
+    band.interior1 = std::max(band.interior0, std::min(s1, end < s.whole.gny ? end - g - kGaussSeamSlack : end));
+    TOPO_TRY(topo_amd_halo_exchange_start(block, s.rows_local, nx, above, below));
+    return run_three(block, band, above, below, [&](const Block& view, int o0, int on) {
+        Block b = view;
+        b.out_row0 = o0;
+        b.out_rows = on;
+        TOPO_TRY(check_block(b, g, g, "shard smoothing"));
+        return launch_gaussian(b, sigma_y, sigma_x, plane + (size_t)(o0 - s0) * nx);
+    }, true);
+}
+
+// The class of the smoothed raster for the kernels that run on it (TPI / STD): what the single GPU's Block(smooth) scans
+// on the whole smoothed plane.  A shard that is the whole raster is scanned like any whole block (the ClassScope of the
+// plane's block does it); a partial one adds up the lattice samples of the OWNED smoothed rows of every rank
+// (topo_amd_shard_classify, collective), so that every sharding takes the same kernels.
+int smoothed_class(const float* owned_plane, const Shard& s, RasterClass* out, bool* whole) {
+    *whole = s.rows_local == s.whole.gny;
+    if (*whole) return TOPO_AMD_OK;
+    TOPO_TRY(topo_amd_shard_classify(owned_plane, s.rows_local, s.row0, s.whole.gny, s.whole.nx));
+    Block b{owned_plane, s.rows_local, s.row0, s.whole.gny, s.whole.nx, s.row0, s.rows_local};
+    TOPO_REQUIRE(declared_class(b, out), "shard smoothing: the class of the smoothed rows was not declared");
+    return TOPO_AMD_OK;
+}
+
+// The smoothed plane of a sharded call: rows [s0, s1) of the shard's smoothed raster, s0 first (workspace 13).  Whatever
+// was remembered or declared for that memory is dropped before it is written and after the call (it is scratch).
+struct SmoothedPlane {
+    float* p = nullptr;
+    int s0 = 0, s1 = 0, nx = 0;
+    int take(int r0, int r1, int n) {
+        s0 = r0;
+        s1 = r1;
+        nx = n;
+        void* w = nullptr;
+        TOPO_TRY(workspace(13, (size_t)(s1 - s0) * nx * sizeof(float), &w));
+        p = (float*)w;
+        forget_plane(p, s1 - s0, nx);
+        return TOPO_AMD_OK;
+    }
+    ~SmoothedPlane() { forget_plane(p, s1 - s0, nx); }
+    const float* row(int r) const { return p + (size_t)(r - s0) * nx; }
+    Block block(int out_row0, int out_rows, int gny) const { return Block{p, s1 - s0, s0, gny, nx, out_row0, out_rows}; }
+};
+}  // namespace
+
+extern "C" {
+
+int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
+                                const int32_t* ksize, const float* angles, int n_angles, int n_planes,
+                                float* norm_out, float* dir_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    return shard_valley_ridge(block, rows_local, row0, gny, nx, taps, ksize, angles, n_angles, n_planes, norm_out, dir_out,
+                              nullptr);
+}
+
+int topo_amd_shard_gaussian(float* block, int rows_local, int row0, int gny, int nx, double sigma_y, double sigma_x,
+                            float* out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(block && out, "shard_gaussian: NULL argument");
+    TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "shard_gaussian: negative sigma");
+    TOPO_REQUIRE(rows_local >= 1 && row0 >= 0 && row0 + rows_local <= gny && nx >= 1,
+                 "shard_gaussian: rows [%d, %d) of a raster of %d rows", row0, row0 + rows_local, gny);
+    const int g = gauss_ghost_rows(sigma_y);  // == topo_amd_halo_rows(GAUSS, sigma_y)
+    TOPO_TRY(shard_view(&block, g, g, "shard_gaussian"));
+    block += shard_view_offset(g, nx);
+    Shard s = make_shard(block, rows_local, row0, gny, nx, g, g);
+    // the vector-ALU or the matrix-core kernels: a property of the WHOLE raster, never of one shard's rows
+    TOPO_TRY(ensure_shard_class(s));
+    ClassScope cls(s.owned);
+    forget_plane(out, rows_local, nx);
+    return smooth_shard_rows(block, s, g, g, sigma_y, sigma_x, g, row0, row0 + rows_local, out);
+}
+
+int topo_amd_shard_tpi_std_smoothed(float* block, int rows_local, int row0, int gny, int nx, int size, double sigma,
+                                    float* tpi_out, float* std_out) {
+    if (!(sigma > 0.0)) return topo_amd_shard_tpi_std(block, rows_local, row0, gny, nx, size, tpi_out, std_out);
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(block, "shard_tpi_std_smoothed: NULL block");
+    TOPO_REQUIRE(rows_local >= 1 && row0 >= 0 && row0 + rows_local <= gny && nx >= 1,
+                 "shard_tpi_std_smoothed: rows [%d, %d) of a raster of %d rows", row0, row0 + rows_local, gny);
+    DiscRuns disc;
+    TOPO_TRY(build_disc(size, &disc));
+    const int up = -disc.dj_min, down = disc.dj_max, g = gauss_ghost_rows(sigma);
+    const int above = up + g, below = down + g;  // == topo_amd_halo_rows(TPI, size, sigma)
+    TOPO_TRY(shard_view(&block, above, below, "shard_tpi_std_smoothed"));
+    block += shard_view_offset(above, nx);
+    Shard s = make_shard(block, rows_local, row0, gny, nx, above, below);
+    // every row the disc reads, smoothed here: the disc step needs no second exchange
+    SmoothedPlane sp;
+    TOPO_TRY(sp.take(std::max(0, row0 - up), std::min(gny, row0 + rows_local + down), nx));
+    {
+        TOPO_TRY(ensure_shard_class(s));
+        ClassScope cls(s.owned);
+        TOPO_TRY(smooth_shard_rows(block, s, above, below, sigma, sigma, g, sp.s0, sp.s1, sp.p));
+    }
+    RasterClass c;
+    bool whole = false;
+    TOPO_TRY(smoothed_class(sp.row(row0), s, &c, &whole));
+    const Block d = sp.block(row0, rows_local, gny);
+    ClassScope cls = whole ? ClassScope(d) : ClassScope(c);
+    forget_plane(tpi_out, rows_local, nx);
+    forget_plane(std_out, rows_local, nx);
+    TOPO_TRY(check_block(d, up, down, "shard_tpi_std_smoothed"));
+    return launch_tpi_std(d, disc, tpi_out, std_out);
+}
+
+int topo_amd_shard_valley_ridge_smoothed(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
+                                         const int32_t* ksize, const float* angles, int n_angles, int n_planes,
+                                         double sigma, float* norm_out, float* dir_out, double* moments_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    if (!(sigma > 0.0))
+        return shard_valley_ridge(block, rows_local, row0, gny, nx, taps, ksize, angles, n_angles, n_planes, norm_out,
+                                  dir_out, moments_out);
+    TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1,
+                 "shard_valley_ridge_smoothed: NULL argument");
+    TOPO_REQUIRE(rows_local >= 1 && row0 >= 0 && row0 + rows_local <= gny && nx >= 1,
+                 "shard_valley_ridge_smoothed: rows [%d, %d) of a raster of %d rows", row0, row0 + rows_local, gny);
+    int up = 0, down = 0;
+    (void)valley_ridge_reach(ksize, n_angles, &up, &down);
+    const int g = gauss_ghost_rows(sigma);
+    const int above = up + g, below = down + g;  // == topo_amd_halo_rows(VALLEY_RIDGE, kmax, sigma)
+    TOPO_TRY(shard_view(&block, above, below, "shard_valley_ridge_smoothed"));
+    block += shard_view_offset(above, nx);
+    Shard s = make_shard(block, rows_local, row0, gny, nx, above, below);
+    SmoothedPlane sp;
+    TOPO_TRY(sp.take(std::max(0, row0 - up), std::min(gny, row0 + rows_local + down), nx));
+    {
+        TOPO_TRY(ensure_shard_class(s));
+        ClassScope cls(s.owned);
+        TOPO_TRY(smooth_shard_rows(block, s, above, below, sigma, sigma, g, sp.s0, sp.s1, sp.p));
+    }
+    // the standardisation of the smoothed field (topo.py:424-427): moments of the owned smoothed rows, all-reduced.
+    // (The valley kernels are chosen by the kernel tables alone, never by the raster class: nothing to classify.)
+    double mean = 0.0, stdev = 0.0;
+    TOPO_TRY(shard_moments(sp.row(row0), rows_local, nx, &mean, &stdev));
+    if (moments_out) {
+        moments_out[0] = mean;
+        moments_out[1] = stdev;
+    }
+    const Block d = sp.block(row0, rows_local, gny);
+    TOPO_TRY(check_block(d, up, down, "shard_valley_ridge_smoothed"));
+    forget_plane(norm_out, rows_local, nx);
+    forget_plane(dir_out, rows_local, nx);
+    return launch_valley_ridge(d, taps, ksize, angles, n_angles, n_planes, mean, stdev, norm_out, dir_out);
+}
+
+int topo_amd_shard_fill_na(float* block, int rows_local, int row0, int gny, int nx, const double* x_coords,
+                           double min_elevation, float* out, uint8_t* missing) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(block, "shard_fill_na: NULL block");
+    TOPO_TRY(shard_view(&block, 0, 0, "shard_fill_na"));
+    block += shard_view_offset(0, nx);  // the owned rows: rows are independent, no exchange
+    // (out == the owned rows: in place; topo_amd_fill_na_dev drops the class declared for them, and the next sharded
+    // call re-classifies collectively - so every rank makes this call, or none)
+    return topo_amd_fill_na_dev(block, rows_local, row0, gny, nx, x_coords, min_elevation, row0, rows_local, out, missing);
 }
 
 }  // extern "C"

@@ -87,7 +87,7 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
-constexpr int kWorkspaces = 13;  // Context::ws slots (12: the fill's wide-row words)
+constexpr int kWorkspaces = 14;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard)
 constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;

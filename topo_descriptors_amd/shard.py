@@ -103,7 +103,8 @@ class RowShardPlan:
 
 
 def halo_rows(descriptor, p0=0.0, p1=0.0):
-    """(above, below) ghost depth of a descriptor, from the library (topo_amd_halo_rows)."""
+    """(above, below) ghost depth of a descriptor, from the library (topo_amd_halo_rows).  ``p1`` of DESC_TPI, DESC_STD
+    and DESC_VALLEY_RIDGE: the pre-smoothing sigma (0: none), whose Gaussian ghost rows are added to the reach."""
     import ctypes as C
 
     from . import _lib
@@ -174,12 +175,50 @@ class ShardedDEM:
         payload = broadcast_bytes(uid.raw if rank == 0 else None)
         _lib.check(lib.topo_amd_comm_init(rank, nranks, payload), "comm_init")
 
-    def tpi_std(self, size, tpi=None, std=None):
-        from . import _lib
+    def tpi_std(self, size, tpi=None, std=None, sigma=None):
+        """Collective.  ``sigma``: the Gaussian pre-smoothing of ``batch.compute_tpi / compute_std(smth_factors=...)``
+        (``topo_amd_shard_tpi_std_smoothed``; the plan's halo must be ``halo_rows(DESC_TPI, size, sigma)``).  None: the
+        un-smoothed call, unchanged."""
         p = self.plan
-        self._collective("topo_amd_shard_tpi_std", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx,
-                                                     int(size), tpi.ptr if tpi else None,
-                                                     std.ptr if std else None)
+        outs = (tpi.ptr if tpi else None, std.ptr if std else None)
+        if sigma is None:
+            self._collective("topo_amd_shard_tpi_std", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, int(size),
+                             *outs)
+            return
+        sig = _sigma_value(sigma, "tpi_std")
+        self._collective("topo_amd_shard_tpi_std_smoothed", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx,
+                         int(size), sig, *outs)
+
+    def gaussian(self, sigma, out):
+        """Collective: ``topo.dem(dem, sigma)`` on this shard's rows into ``out`` (rows_local x nx).  ``sigma``: a scalar
+        or an (axis 0, axis 1) pair; the plan's halo must be ``halo_rows(DESC_GAUSS, sigma_y)``."""
+        p = self.plan
+        sy, sx = _sigma_pair(sigma)
+        self._collective("topo_amd_shard_gaussian", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, sy, sx, out.ptr)
+
+    def fill_na(self, out=None, missing=None, x_coords=None, min_elevation=None):
+        """Collective by contract: gaps of the owned rows filled with the nearest valid sample along x
+        (``Block.fill_na``'s rules).  ``out``: a float32 DeviceArray of rows_local x nx, or None to fill the shard's own
+        rows in place (their raster class is then derived again, by all ranks together, at the next descriptor call:
+        every rank makes this call, or none).  ``missing``: a uint8 DeviceArray of rows_local x nx or None;
+        ``x_coords``: the whole DEM's, one per column, or None (the column index)."""
+        import ctypes as C
+
+        from . import _lib
+        from .helpers import _fill_coords
+        p = self.plan
+        x = _fill_coords(x_coords, p.nx)
+        if missing is not None and missing.dtype != np.uint8:
+            raise ValueError("ShardedDEM.fill_na: the missing mask is a uint8 DeviceArray")
+        for name, a in (("out", out), ("missing", missing)):
+            if a is not None and (a.rows, a.nx) != (p.rows_local, p.nx):
+                raise ValueError(f"ShardedDEM.fill_na: {name} has {a.rows} x {a.nx}, the shard owns {p.rows_local} x {p.nx}")
+        m = np.nan if min_elevation is None else float(min_elevation)
+        # (the owned rows: the library finds them at the declared layout's offset, out = them for the in-place fill)
+        dst = self.block.row_ptr(p.halo_above) if out is None else out.ptr
+        self._collective("topo_amd_shard_fill_na", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx,
+                         None if x is None else x.ctypes.data_as(_lib._f64p), m, C.c_void_p(dst),
+                         missing.ptr if missing is not None else None)
 
     def gradient(self, sigma, res_x, res_y, sig_ratio=1.0, dx=None, dy=None, slope=None, aspect=None):
         from . import _lib
@@ -195,17 +234,26 @@ class ShardedDEM:
                                                       float(sigma), float(sig_ratio), mode,
                                                       _lib.ptr(rx), _lib.ptr(ry), *outs)
 
-    def valley_ridge(self, taps, ksize, angles, n_planes, norm, direction):
-        """Collective.  The plan's halo must be ``halo_rows(DESC_VALLEY_RIDGE, ksize.max())``; the mean
-        and standard deviation of the whole DEM are formed inside (one all-reduce)."""
+    def valley_ridge(self, taps, ksize, angles, n_planes, norm, direction, sigma=None, moments=False):
+        """Collective.  The plan's halo must be ``halo_rows(DESC_VALLEY_RIDGE, ksize.max(), sigma or 0)``; the mean
+        and standard deviation of the whole DEM (with ``sigma``: of the whole smoothed DEM, topo.py:424-427) are formed
+        inside (one all-reduce).  ``moments=True``: returns the (mean, std) the call standardised with; otherwise None."""
         from . import _lib
         p = self.plan
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         ksize = np.ascontiguousarray(ksize, dtype=np.int32)
         angles = np.ascontiguousarray(angles, dtype=np.float32)
-        self._collective("topo_amd_shard_valley_ridge", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, taps.ctypes.data_as(_lib._vp),
-            ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes),
-            norm.ptr, direction.ptr)
+        tables = (taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp),
+                  ksize.size, int(n_planes))
+        if sigma is None and not moments:
+            self._collective("topo_amd_shard_valley_ridge", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, *tables,
+                             norm.ptr, direction.ptr)
+            return None
+        sig = 0.0 if sigma is None else _sigma_value(sigma, "valley_ridge")
+        mom = np.zeros(2, dtype=np.float64)
+        self._collective("topo_amd_shard_valley_ridge_smoothed", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx,
+                         *tables, sig, norm.ptr, direction.ptr, mom.ctypes.data_as(_lib._f64p))
+        return (float(mom[0]), float(mom[1])) if moments else None
 
     def sx(self, dj, di, dist, window, height, out):
         from . import _lib
@@ -232,6 +280,30 @@ class ShardedDEM:
         self._collective("topo_amd_shard_sx_multi", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, len(sectors), first.ctypes.data_as(_lib._i32p),
             dj.ctypes.data_as(_lib._i32p), di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p),
             window.ctypes.data_as(_lib._i32p), float(height), planes)
+
+
+def _sigma_value(sigma, who):
+    """A pre-smoothing sigma as the C ABI takes it, refused unless a finite number >= 0 - before any library call."""
+    try:
+        v = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"ShardedDEM.{who}: sigma must be a number, got {sigma!r}") from None
+    if not np.isfinite(v) or v < 0.0:
+        raise ValueError(f"ShardedDEM.{who}: sigma must be finite and >= 0, got {v}")
+    return v
+
+
+def _sigma_pair(sigma):
+    """(sigma_y, sigma_x) of a scalar or an (axis 0, axis 1) pair, like ``topo.dem``; refused before any library call."""
+    try:
+        a = np.asarray(sigma, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"ShardedDEM.gaussian: sigma must be a number or a (y, x) pair, got {sigma!r}") from None
+    if a.ndim == 0:
+        a = np.repeat(a, 2)
+    if a.shape != (2,):
+        raise ValueError(f"ShardedDEM.gaussian: sigma is a scalar or a (y, x) pair, got shape {a.shape}")
+    return tuple(_sigma_value(v, "gaussian") for v in a)
 
 
 def sx_multi_halo(sectors):
