@@ -10,17 +10,23 @@ N contiguous row blocks - the total work is fixed (strong scaling) - and every s
 refreshes the 33 ghost rows from the neighbours over RCCL, overlapped with the interior rows.
 Inputs are generated on the device and are resident in HBM before the timed region.
 
-With N > 1 the line also carries `descriptors`: STD and TPI+STD at 67 px, the gradient at sigma 3.25 and 30.25 and Sx
-(azimuth 0, radius 500 m) through the sharded entry points (topo_amd_shard_*), each with its own ghost-row exchange
-per step - BASELINE.json's "per descriptor" metric for configs[4].  TOPO_AMD_HALO_LOOPBACK=1 with one rank
+A plain run does only what the headline needs: set-up, the clock ramp and warm-up, the K timed steps, --dump-outputs
+and the result line.  Everything else it can measure or check runs with --full only, after the timed steps: see below.
+
+With --full and N > 1 the line also carries `descriptors`: STD and TPI+STD at 67 px, the gradient at sigma 3.25 and
+30.25 and Sx (azimuth 0, radius 500 m) through the sharded entry points (topo_amd_shard_*), each with its own ghost-row
+exchange per step - BASELINE.json's "per descriptor" metric for configs[4].  TOPO_AMD_HALO_LOOPBACK=1 with one rank
 (`python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1`) runs the same sharded steps on ONE GPU
 as the middle shard of three whose neighbours are itself: the exchange is real (ncclSend / ncclRecv on the
 communication stream), the scaling is not.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the TPI kernel at SURVEY.md 8(d)'s 8 B/pixel
 (4 read + 4 written) against 8 TB/s (and, as `frac_read_only_basis`, at north_star's literal
-"HBM-read" 4 B/pixel); `cpu_baseline` times the oracle's scipy restatement of the reference path
-on one host core for a bounded sample.  torch is used for rendezvous, barriers and the
+"HBM-read" 4 B/pixel) from the timed steps' own HIP events.  With --full (one block) the line adds
+`roofline.hbm_copy_live`, `cpu_baseline` (the oracle's scipy restatement of the reference path on one
+host core for a bounded sample) and `cpu_baseline_all_cores`, `parity_spot`, the per-descriptor
+tables `descriptors` and `descriptors_at_config_sizes`, and `end_to_end`; --no-cpu, --no-extras and
+--no-end-to-end leave parts of that out.  torch is used for rendezvous, barriers and the
 max-over-ranks only; it never touches the GPU.
 
 Timing: `value` and `ms_per_step` come from the wall clock around exactly K steps between two
@@ -62,11 +68,14 @@ def parse():
     ap.add_argument("--ny", type=int, default=32768)
     ap.add_argument("--nx", type=int, default=32768)
     ap.add_argument("--size", type=int, default=67, help="disc diameter in pixels (2000 m / 30 m)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-descriptor side table")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline does not need: the live HBM copy, the CPU "
+                         "baselines and parity spots, the per-descriptor tables and the end_to_end section")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-descriptor side table")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the host-buffer end_to_end section (it launches the headline kernel on a 16384^2 DEM: under "
-                         "rocprofv3 --stats those launches would enter the kernel's average duration)")
+                    help="with --full: skip the host-buffer end_to_end section (it launches the headline kernel on a "
+                         "16384^2 DEM: under rocprofv3 --stats those launches would enter the kernel's average duration)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the TPI plane of the last step as DIR/tpi.npy (a fixed, seeded "
                          "sample of whole rows, at most 32 MB) and their row indices as DIR/tpi_rows.npy")
@@ -644,7 +653,8 @@ def main():
 
         shard_mod.ShardedDEM.init_comm(rank, world, rdv.bcast_bytes)
         # one buffer for every descriptor of the table: ghost zones as deep as the deepest asks for (the gradient
-        # at sigma 30.25: 122 rows); each call uses the rows next to the owned ones (topo_amd_shard_layout)
+        # at sigma 30.25: 122 rows); each call uses the rows next to the owned ones (topo_amd_shard_layout).  A plain
+        # run, which has no table, allocates the same depth: its timed steps run on the layout of a --full run
         deep = max(max(shard_mod.halo_rows(_lib.DESC_TPI, size)),
                    0 if args.no_extras else max(shard_mod.halo_rows(_lib.DESC_GRADIENT, 30.25, 1.0)))
         if loopback:  # the middle shard of three; its neighbours are itself
@@ -782,7 +792,8 @@ def main():
                 "algorithmic_bytes_per_pixel": BYTES_PER_PIXEL["tpi"],
             },
         }
-        if not sharded:
+        # --full only from here on: nothing below enters the headline, and a plain run does none of it
+        if args.full and not sharded:
             # what the memory system gives a kernel that does NOTHING but move the same 8 B/pixel (round 6): the runtime's
             # device-to-device copy of the DEM plane into the output plane, timed like the kernel (HIP events on the compute
             # stream, behind the timed region).  tools/ubench/strip_copy.hip measures the same with the kernels' own access
@@ -805,7 +816,7 @@ def main():
                 d.sync()
             except Exception as exc:  # noqa: BLE001
                 result["roofline"]["hbm_copy_live"] = {"error": repr(exc)}
-        if not args.no_cpu and not sharded:
+        if args.full and not args.no_cpu and not sharded:
             rows_s = min(ny, 16384)  # ~4 s of scipy on one core + ~6 s of the C twin on all of them
             cols_s = min(nx, 16384)
             sample = block.to_host(first_row, rows_s)[:, :cols_s].copy()
@@ -824,12 +835,12 @@ def main():
                 "checker": "oracle.tpi_scipy (the reference's scipy.signal.convolve call)",
             }
             result["parity_spot"].update(parity_spots(d, block, first_row, nx))
-        if not args.no_extras and not sharded:
+        if args.full and not args.no_extras and not sharded:
             result["descriptors"] = extras(d, _lib, args, d.Block, block, ny, nx)
             result["descriptors_at_config_sizes"] = config_rows(d)
             if not args.no_end_to_end:
                 result["end_to_end"] = end_to_end(d, _lib, size)
-    if not args.no_extras and sharded:  # collective: every rank takes part, rank 0 reports
+    if args.full and not args.no_extras and sharded:  # collective: every rank takes part, rank 0 reports
         outs, steps_by_key = sharded_steps(sd, d, rows_local, nx)
         table = sharded_descriptors(rdv, steps_by_key, d.time_launches, px_total, world)
         d.sync()

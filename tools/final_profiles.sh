@@ -40,11 +40,11 @@ PMC_EXTRA="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_MFMA SQ
 cp gpurun_out/final/pmc_valley/summary.txt $F/r06_valley_pmc_summary.txt
 # (the Sx kernels' counters: profiles/r02_sx_pmc_summary.txt stands for the axis-aligned scans; PMC_SCRIPT=tools/sx_trace.py re-takes them)
 # the sharded step with the real exchange on one GPU: one 4096-row shard of the 8-GPU split, neighbours = itself
-TOPO_AMD_HALO_LOOPBACK=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --ny 4096 > $F/r06_bench_loopback_4096rows.json 2> $F/loopback.err
-python3 bench.py > $F/r06_bench.json 2> $F/r06_bench.err
+TOPO_AMD_HALO_LOOPBACK=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --ny 4096 --full > $F/r06_bench_loopback_4096rows.json 2> $F/loopback.err
+python3 bench.py --full > $F/r06_bench.json 2> $F/r06_bench.err
 cd /tmp && export TMPDIR=/tmp
 # (--no-end-to-end: that section launches tpi_march_kernel<67> on a 16384^2 DEM, which would enter the kernel's average)
-rocprofv3 --kernel-trace --stats --output-format csv -d $F/trace -o bench -- python3 $R/bench.py --no-end-to-end > $F/r06_bench_under_rocprof.json 2> $F/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $F/trace -o bench -- python3 $R/bench.py --full --no-end-to-end > $F/r06_bench_under_rocprof.json 2> $F/trace.err
 cp $F/trace/bench_kernel_stats.csv $F/r06_bench_kernel_stats.csv 2>/dev/null
 rm -rf $R/gpurun_out/final/pmc_*/pass*/  # the raw counter files are large
 ls -la $F

@@ -30,7 +30,7 @@ for N in 2 4 8; do
     echo "== N=$N gate=$MODE" | tee -a "$OUT/summary.txt"
     HSA_ENABLE_IPC_MODE_LEGACY=0 NCCL_DEBUG=INFO NCCL_DEBUG_SUBSYS=INIT,P2P TOPO_AMD_GATE_MODE=$MODE \
       timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps "$STEPS" --warmup 5 > "$LOG" 2>&1
+      bench.py --gpus "$N" --steps "$STEPS" --warmup 5 --full > "$LOG" 2>&1
     echo "   exit code $?" | tee -a "$OUT/summary.txt"
     # the bench line (last line that parses as JSON) - value, ms per step, gate give-ups, shard table
     python - "$LOG" <<'PY' | tee -a "$OUT/summary.txt"
