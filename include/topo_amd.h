@@ -273,6 +273,10 @@ int topo_amd_valley_ridge_dev(const float* in, int in_rows, int in_row0, int gny
  * + 8: the matrix pipe ran over pairs of opposite cells (point-symmetric tables); + 16: with the pixel operands streamed
  * in chunks (more than 240 pairs: kernels of 19 px and more).                                                            */
 int topo_amd_valley_route(int* route);
+/* Which kernel the calling thread's last TPI / STD disc call (topo_amd_tpi_std_dev and the calls built on it) finished
+ * its whole-metre tiles with (for tests and diagnostics): 1 the wide ring (TPI alone, 67 px, a single block of a
+ * whole-metre raster class: csrc/disc_ring_wide_impl.hpp), 0 any other kernel.                                        */
+int topo_amd_tpi_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);

@@ -13,6 +13,12 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
+    python tools/valu_bound.py wide > profiles/r07_tpi67_wide_valu_count.json
+
+wide: the row loop of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
+row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
+row loop per VALID output column: offline, before any GPU time.
+
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
 the loop are counted next to it (they issue beside the vector ones of the other waves of the SIMD).
@@ -44,7 +50,77 @@ def half_rate(op):
             op.startswith("v_writelane"))
 
 
+WIDE_KERNEL = "tpi_ring_wide_kernelILi67"
+WIDE_SRC = """#include "disc_wave_impl.hpp"
+namespace topo { int wide_probe(const Block& b, float* t) { return launch_ring_wide<67>(b, t, 60, 184); } }
+"""
+
+
+def loop_ops(txt, kernel, pick):
+    """The VALU / LDS mnemonics of the smallest loop of `kernel` (mangled name prefix) that `pick(ops)` accepts."""
+    start = txt.index(kernel + SUFFIX)
+    lines = txt[start:txt.index("s_endpgm", start)].split("\n")
+    labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
+    best = None
+    for i, l in enumerate(lines):
+        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.search(r"s_branch\s+(\.LBB\d+_\d+)", l)
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            a = labels[m.group(1)]
+            o = [x.strip().split()[0] for x in lines[a:i + 1]
+                 if x.strip() and not x.strip().startswith((".", ";", "//")) and not x.strip().endswith(":")]
+            if pick(o) and (best is None or len(o) < len(best)):
+                best = o
+    return best
+
+
+def price(o):
+    valu = [x for x in o if x.startswith("v_")]
+    kinds = Counter()
+    for x in valu:
+        kinds["dpp" if "_dpp" in x else "add3" if "add3" in x else "f64_or_convert" if ("f64" in x or x.startswith("v_cvt")) else
+              "other_half_rate" if half_rate(x) else "plain"] += 1
+    mix = Counter("half" if half_rate(x) else "plain" for x in valu)
+    return valu, kinds, mix["plain"] * NS_PLAIN + mix["half"] * NS_HALF
+
+
+def wide():
+    csrc = os.path.join(REPO, "topo_descriptors_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        src, asm = os.path.join(tmp, "wide.hip"), os.path.join(tmp, "wide.s")
+        open(src, "w").write(WIDE_SRC)
+        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
+                        "-I", csrc, "-I", os.path.join(REPO, "include"), src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
+        txt = open(asm).read()
+        lab = os.path.join(tmp, "lab.s")
+        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S",
+                        "--cuda-device-only", os.path.join(REPO, "tools", "ubench", "tpi_lab.hip"), "-o", lab],
+                       check=True, stderr=subprocess.DEVNULL)
+        txt_m = open(lab).read()
+    # the chain loop: one output row per trip (42 prefix-row reads in two pieces each, the float64 finalisation)
+    o = loop_ops(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b128" for x in o) >= 42 and sum(x == "ds_read_b64" for x in o) >= 42
+                 and any("f64" in x for x in o))
+    om = loop_ops(txt_m, KERNEL, lambda o: 42 <= sum(x == "ds_read_b128" for x in o) <= 46 and any("f64" in x for x in o))
+    valu, kinds, ns = price(o)
+    valu_m, kinds_m, ns_m = price(om)
+    cols, cols_m = 312, TILE_W
+    print(json.dumps({
+        "kernel": "tpi_ring_wide_kernel<67>, row loop (one output row of 52 lanes x 6 columns)",
+        "row_loop_instructions": {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128"),
+                                  "ds_read_b64": o.count("ds_read_b64"), "salu": sum(1 for x in o if x.startswith("s_"))},
+        "ns_per_wave_row": round(ns, 1),
+        "valid_columns_per_wave_row": cols,
+        "marching_kernel": {"kernel": "tpi_march_kernel<67, 60, 12, true, true, true>", "valu": len(valu_m), "by_kind": dict(kinds_m),
+                            "ns_per_wave_row": round(ns_m, 1), "valid_columns_per_wave_row": cols_m},
+        "valu_per_valid_column": {"wide": round(len(valu) / cols, 3), "marching": round(len(valu_m) / cols_m, 3)},
+        "ns_per_valid_column": {"wide": round(ns / cols, 3), "marching": round(ns_m / cols_m, 3)},
+        "valu_ns_per_valid_column_saved": round(1.0 - (ns / cols) / (ns_m / cols_m), 3),
+        "issue_cost_ns_per_wave_instruction_and_simd": {"plain": NS_PLAIN, "half_rate": NS_HALF},
+    }, indent=1))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "wide":
+        return wide()
     std = len(sys.argv) > 1 and sys.argv[1] == "std"
     if std:
         del sys.argv[1]

@@ -512,6 +512,7 @@ int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float*
 // host-buffer call spends most of its time on (tools/ubench/page_touch.cpp: 92 ms per GiB against 19 ms
 // for the copy itself).  prefault() asks for huge pages and touches the array from a few threads
 // while the upload and the kernels run; ready() joins them before the first download.
+thread_local int t_tpi_route = 0;     // 1: the calling thread's last TPI / STD disc call took the wide ring (topo_amd_tpi_route)
 thread_local int t_valley_route = 0;  // the evaluation the calling thread's last valley / ridge call took (topo_amd_valley_route)
 thread_local int t_host_chunks = 0;  // row chunks of the calling thread's last host-buffer call (topo_amd_host_chunks)
 struct HostRun {
@@ -793,6 +794,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
 
 }  // namespace
 
+void note_tpi_route(int route) { t_tpi_route = route; }
 void note_valley_route(int route) { t_valley_route = route; }
 
 }  // namespace topo
@@ -1004,6 +1006,12 @@ int topo_amd_release_host_planes(void) {
     }
     c.host_planes.clear();
     c.host_plane_bytes.clear();
+    return TOPO_AMD_OK;
+}
+
+int topo_amd_tpi_route(int* route) {
+    TOPO_REQUIRE(route != nullptr, "tpi_route: NULL output");
+    *route = t_tpi_route;
     return TOPO_AMD_OK;
 }
 

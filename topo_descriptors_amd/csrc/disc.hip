@@ -426,6 +426,7 @@ int launch_tpi_std(const Block& b, const DiscRuns& disc, float* tpi_out, float* 
     if (c.seams.n > 0 && !(disc_wave_covers(disc.size) && b.nx % 4 == 0 && (reinterpret_cast<uintptr_t>(b.in) & 15) == 0 &&
                            (reinterpret_cast<uintptr_t>(std_out) & 15) == 0 && (reinterpret_cast<uintptr_t>(tpi_out) & 15) == 0))
         c.seams.n = 0;
+    note_tpi_route(0);  // (the wide ring's launcher sets 1)
     {
         int r = launch_disc_wave(b, disc.size, tpi_out, std_out);
         if (r == TOPO_AMD_EUNSUP && disc_wave_covers(disc.size) && b.nx >= 4)

@@ -2221,6 +2221,7 @@ int launch_wave(const Block& b, float* tpi_out, float* std_out, bool only_deferr
 }  // namespace topo
 
 #include "disc_ring_impl.hpp"
+#include "disc_ring_wide_impl.hpp"
 
 namespace topo {
 
@@ -2261,6 +2262,15 @@ constexpr int tpi_ring_min_size() { return 5; }
 // 13.61; TPI + STD 67 px 10.86 / 14.22.  Identical bits (CRC-32 of both planes, whole metres and fractional DEM).
 constexpr int std_ring_min_size() { return 5; }
 constexpr int tpi_ring_max_size() { return 17; }
+// Disc sizes TPI alone takes the wide ring for (disc_ring_wide_impl.hpp: 6 columns per lane, staging waves apart), in front of
+// the scaled pass and the general kernel: whole-metre raster class, single-block calls.
+constexpr int tpi_wide_min_size() { return 67; }
+constexpr int tpi_wide_max_size() { return 67; }
+// (lab switch: TOPO_AMD_TPI_WIDE_RING=0 keeps the marching kernel, for the A/B)
+inline bool tpi_wide_ring() {
+    static const int v = env_int("TOPO_AMD_TPI_WIDE_RING", 1);
+    return v != 0;
+}
 // TOPO_AMD_TPI_FRACTION_EXACT=1: tiles with fractional elevations take the exact two-pass route (2^-16 m) instead of the
 // scaled one-chain route (2^-8 m, tpi_scaled_march_kernel)
 inline bool tpi_fraction_scaled() {
@@ -2383,6 +2393,19 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
         // small discs: the general kernel's two passes over one tile beat two marching kernels
         TOPO_TRY((launch_march<SIZE, TH12, 12, true, false, false>(b, tpi_out)));
         return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+    }
+    if constexpr (tpi_wide_ring_fits(SIZE) && SIZE >= tpi_wide_min_size() && SIZE <= tpi_wide_max_size()) {
+        // whole metres, one block: the wide ring computes the phases whose windows hold whole metres and marks the marching
+        // geometry's tiles of the others (fractional, non-finite or absurd samples) for the scaled pass, which leaves what it
+        // cannot take to the general kernel - the marching route's two followers on the marching route's map
+        const bool one_block = b.out_row0 == 0 && b.out_rows == b.gny && ctx().seams.n == 0;
+        if (tpi_wide_ring() && tpi_fraction_scaled() && one_block && current_class().frac_share == 0.0f &&
+            !dem_memo_mostly_fractional(b)) {
+            TOPO_TRY((launch_ring_wide<SIZE>(b, tpi_out, TH12, Geo<SIZE>::TILE_W)));
+            note_tpi_route(1);
+            TOPO_TRY((launch_scaled_march<SIZE, TH12, 12>(b, tpi_out)));
+            return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+        }
     }
     if (tpi_fraction_scaled()) {
         // fractional tiles: one chain on x in units of 2^-8 m (tpi_scaled_march_kernel: <= 1.95 mm, see there)

@@ -125,6 +125,14 @@ def host_chunks():
     return n.value
 
 
+def tpi_route():
+    """The kernel the calling thread's last TPI / STD disc call took for its whole-metre tiles: 1 the wide ring
+    (``csrc/disc_ring_wide_impl.hpp``: TPI alone at 67 px on a single block of a whole-metre raster class), 0 any other."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().topo_amd_tpi_route(C.byref(n)), "tpi_route")
+    return n.value
+
+
 def valley_route():
     """The evaluation the calling thread's last valley / ridge call took: 0 tap by tap (``csrc/valley.hip``), 1 matrix pipe
     (``csrc/valley_mfma.hip``), 2 FFT; + 4 when the tap-by-tap kernel followed the matrix pipe over its flagged tiles; + 8 when the
