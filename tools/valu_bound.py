@@ -15,9 +15,12 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
 
     python tools/valu_bound.py wide > profiles/r07_tpi67_wide_valu_count.json
 
-wide: the row loop of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
+wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
-row loop per VALID output column: offline, before any GPU time.
+row loop per VALID output column: offline, before any GPU time.  A chain wave's two rows of a phase are unrolled into
+the phase loop (three ds_read_b64 per prefix row), and the first row is the stretch from its s_setprio 3 to the second
+row's s_setprio 1 (its own reads after the two it leads with, the chain, the finalisation and the stores, then the
+second row's two leading reads).  Vector adds whose result is a ds_read address are counted as their own class.
 
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
@@ -56,8 +59,8 @@ namespace topo { int wide_probe(const Block& b, float* t) { return launch_ring_w
 """
 
 
-def loop_ops(txt, kernel, pick):
-    """The VALU / LDS mnemonics of the smallest loop of `kernel` (mangled name prefix) that `pick(ops)` accepts."""
+def loop_lines(txt, kernel, pick):
+    """The instruction lines of the smallest loop of `kernel` (mangled name prefix) whose mnemonics `pick(ops)` accepts."""
     start = txt.index(kernel + SUFFIX)
     lines = txt[start:txt.index("s_endpgm", start)].split("\n")
     labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
@@ -66,11 +69,34 @@ def loop_ops(txt, kernel, pick):
         m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.search(r"s_branch\s+(\.LBB\d+_\d+)", l)
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             a = labels[m.group(1)]
-            o = [x.strip().split()[0] for x in lines[a:i + 1]
+            o = [x.strip() for x in lines[a:i + 1]
                  if x.strip() and not x.strip().startswith((".", ";", "//")) and not x.strip().endswith(":")]
-            if pick(o) and (best is None or len(o) < len(best)):
+            if pick([x.split()[0] for x in o]) and (best is None or len(o) < len(best)):
                 best = o
     return best
+
+
+def loop_ops(txt, kernel, pick):
+    """The mnemonics of loop_lines."""
+    o = loop_lines(txt, kernel, pick)
+    return None if o is None else [x.split()[0] for x in o]
+
+
+def address_adds(lines):
+    """Vector adds whose result register is the address of a ds_read before it is written again."""
+    n = 0
+    for i, x in enumerate(lines):
+        if not x.startswith("v_add_u32"):
+            continue
+        dst = x.split()[1].rstrip(",")
+        for y in lines[i + 1:]:
+            f = y.replace(",", " ").split()
+            if f[0].startswith("ds_read") and len(f) > 2 and f[2] == dst:
+                n += 1
+                break
+            if f[0].startswith("v_") and len(f) > 1 and f[1] == dst:
+                break
+    return n
 
 
 def price(o):
@@ -96,17 +122,27 @@ def wide():
                         "--cuda-device-only", os.path.join(REPO, "tools", "ubench", "tpi_lab.hip"), "-o", lab],
                        check=True, stderr=subprocess.DEVNULL)
         txt_m = open(lab).read()
-    # the chain loop: one output row per trip (42 prefix-row reads in two pieces each, the float64 finalisation)
-    o = loop_ops(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b128" for x in o) >= 42 and sum(x == "ds_read_b64" for x in o) >= 42
-                 and any("f64" in x for x in o))
+    # the phase loop with both rows of a chain wave (2 x 42 prefix rows, three ds_read_b64 each, the float64 finalisation);
+    # one row: from the first row's s_setprio 3 to the second row's s_setprio 1
+    ph = loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 2 * 3 * 42 and any("f64" in x for x in o))
+    mn = [x.split()[0] for x in ph]
+    a = next(i for i, x in enumerate(ph) if x == "s_setprio 3")
+    b = next(i for i, x in enumerate(ph) if i > a and x == "s_setprio 1")
+    row = ph[a:b]
+    o = [x.split()[0] for x in row]
+    assert mn.count("ds_read_b64") == 2 * o.count("ds_read_b64") == 2 * 3 * 42, "one row: 42 prefix rows of three reads"
+    n_addr = address_adds(row)
     om = loop_ops(txt_m, KERNEL, lambda o: 42 <= sum(x == "ds_read_b128" for x in o) <= 46 and any("f64" in x for x in o))
     valu, kinds, ns = price(o)
     valu_m, kinds_m, ns_m = price(om)
+    kinds["plain"] -= n_addr  # (plain adds: priced as before)
+    kinds["ds_read_address"] = n_addr
     cols, cols_m = 312, TILE_W
     print(json.dumps({
-        "kernel": "tpi_ring_wide_kernel<67>, row loop (one output row of 52 lanes x 6 columns)",
+        "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns) of the phase loop",
         "row_loop_instructions": {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128"),
-                                  "ds_read_b64": o.count("ds_read_b64"), "salu": sum(1 for x in o if x.startswith("s_"))},
+                                  "ds_read_b64": o.count("ds_read_b64"), "v_mov_b32_dpp": o.count("v_mov_b32_dpp"),
+                                  "s_nop": o.count("s_nop"), "salu": sum(1 for x in o if x.startswith("s_"))},
         "ns_per_wave_row": round(ns, 1),
         "valid_columns_per_wave_row": cols,
         "marching_kernel": {"kernel": "tpi_march_kernel<67, 60, 12, true, true, true>", "valu": len(valu_m), "by_kind": dict(kinds_m),

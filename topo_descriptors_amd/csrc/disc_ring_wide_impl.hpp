@@ -6,9 +6,12 @@
 //
 //   * a lane owns NCW = 6 adjacent columns: 6 lane hops per side for 67 px, 52 of 64 lanes valid (312 of 384 staged
 //     columns), the chain two-sided and rim first as in ring_disc_sum (disc_ring_impl.hpp);
-//   * a ring row is 384 dwords (1.5 KiB) in two pieces: lane l keeps its columns 0-3 at dword 4 l and 4-5 at dword
-//     256 + 2 l, so a prefix row is one conflict-free ds_read_b128 (1 KiB per wave) and one ds_read_b64 (512 B);
-//   * the ring holds R = SIZE + 32 rows and the staging runs on waves of its own (std_ring_spec_kernel's structure):
+//   * a ring row is 384 dwords (1.5 KiB), staged column c at dword c: lane l reads its 6 columns as three ds_read_b64 at
+//     +0, +8 and +16 from byte 24 l (dwords 6 l, 6 l + 1 of the 32 lanes of a group are distinct mod 64: conflict-free);
+//   * the ring holds R = SIZE + 32 rows plus GR = 6 guard rows behind them, copies of slots 0 .. GR - 1 (WideCfg), so
+//     that one VGPR address at slot (s0 + k) mod R reaches the rows k .. k + GR of the window by immediate offsets: nine
+//     addresses a row (WBase) instead of one per read;
+//   * the staging runs on waves of its own (std_ring_spec_kernel's structure):
 //     waves 0-2 convert, classify and write batch ph + 1 (16 rows, two columns per lane, 8-byte loads) and issue the
 //     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase;
 //   * prefix sums are uint32 modulo 2^32 with no offset and the finalisation is tpi_march_kernel's expression, so the
@@ -91,11 +94,12 @@ struct WideCfg {
     static constexpr int TH = 64;       // rows of a work tile (the blocks' runs are made of these)
     static constexpr int PPT = TH / B;
     static constexpr int R = SIZE + 2 * B;  // the window of a phase and the batch staged beside it
+    static constexpr int GR = 6;            // guard rows: slot R + s holds what slot s holds (s < GR)
     static constexpr int HALO = SIZE - 1;
     static constexpr int PAD = 1 + (B - (1 + HALO + B) % B) % B;
     static constexpr int PRO = PAD + HALO + B;
     static constexpr int NB_PRO = PRO / B;  // batches a phase's window touches
-    static constexpr size_t LDS = (size_t)R * G::W * sizeof(uint32_t) + 2 * SW * sizeof(int) + 16;
+    static constexpr size_t LDS = (size_t)(R + GR) * G::W * sizeof(uint32_t) + 2 * SW * sizeof(int) + 16;
     static_assert(SW * 128 == G::W, "two staged columns per staging lane");
     static_assert(TH % B == 0 && PRO % B == 0, "whole batches");
     static_assert(LDS <= 160 * 1024, "ring does not fit LDS");
@@ -103,14 +107,61 @@ struct WideCfg {
 };
 
 constexpr bool tpi_wide_ring_fits(int size) {
-    return size >= 5 && size % 2 == 1 && (size_t)(size + 32) * 384 * 4 + 64 <= 160 * 1024 && 64 - 2 * ((size / 2 + 5) / 6) >= 16;
+    return size >= 5 && size % 2 == 1 && (size_t)(size + 32 + 6) * 384 * 4 + 64 <= 160 * 1024 && 64 - 2 * ((size / 2 + 5) / 6) >= 16;
 }
 
-// dword of staged column c in a ring row
-__device__ __forceinline__ int wide_dword_of_column(int c) {
-    const int l = c / NCW, s = c - NCW * l;
-    return s < 4 ? 4 * l + s : 256 + 2 * l + (s - 4);
-}
+// The VGPR addresses of a row's prefix-row reads.  The chain reads run r at Q indices top = run_hi + 1 + M and
+// bot = run_lo + M, in the order WGeo::S.order.  A base at Q index kb is the one VGPR 24 lane + ((s0 + kb) mod R) PB; a read
+// at k with kb <= k <= kb + GR is that base plus the immediate (k - kb) PB (+0, +8, +16): it lands in slot
+// (s0 + kb) mod R + k - kb <= R - 1 + GR, a guard row where the ring wraps.  The bases cover the read indices greedily from
+// the smallest, and each is formed at the first fetch that needs it (so it lives only over its stretch of the sweep).
+template <int SIZE, int GR>
+struct WBase {
+    using G = WGeo<SIZE>;
+    static constexpr int NR = G::NR;
+    struct Tab {
+        int nb;           // bases
+        int kb[2 * SIZE]; // Q index of base b
+        int first[2 * SIZE];  // fetch (index into S.order) that forms base b
+        int top_b[SIZE], bot_b[SIZE];  // per fetch i: base of the top / bottom read
+        int top_k[SIZE], bot_k[SIZE];  // per fetch i: Q index of the top / bottom read
+    };
+    static constexpr Tab make() {
+        Tab t{};
+        bool need[2 * SIZE + 2] = {};
+        for (int i = 0; i < NR; ++i) {
+            const int r = G::S.order[i];
+            t.top_k[i] = G::T.run_hi[r] + 1 + G::M;
+            t.bot_k[i] = G::T.run_lo[r] + G::M;
+            need[t.top_k[i]] = need[t.bot_k[i]] = true;
+        }
+        t.nb = 0;
+        for (int k = 0; k <= 2 * G::M + 1; ++k)
+            if (need[k] && (t.nb == 0 || k > t.kb[t.nb - 1] + GR)) t.kb[t.nb++] = k;
+        for (int b = 0; b < t.nb; ++b) t.first[b] = NR;
+        auto base_of = [&](int k) {
+            int b = 0;
+            while (b + 1 < t.nb && t.kb[b + 1] <= k) ++b;
+            return b;
+        };
+        for (int i = 0; i < NR; ++i) {
+            t.top_b[i] = base_of(t.top_k[i]);
+            t.bot_b[i] = base_of(t.bot_k[i]);
+            if (i < t.first[t.top_b[i]]) t.first[t.top_b[i]] = i;
+            if (i < t.first[t.bot_b[i]]) t.first[t.bot_b[i]] = i;
+        }
+        return t;
+    }
+    static constexpr Tab T = make();
+    static constexpr bool check() {
+        for (int i = 0; i < NR; ++i)
+            if (T.top_k[i] - T.kb[T.top_b[i]] > GR || T.top_k[i] < T.kb[T.top_b[i]] || T.bot_k[i] - T.kb[T.bot_b[i]] > GR ||
+                T.bot_k[i] < T.kb[T.bot_b[i]])
+                return false;
+        return true;
+    }
+    static_assert(check(), "every read within GR rows of its base");
+};
 
 #ifndef WIDE_LEAD
 #define WIDE_LEAD 2
@@ -120,46 +171,58 @@ __device__ __forceinline__ int wide_dword_of_column(int c) {
 #endif
 
 typedef uint32_t u32x2w __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const char lds_char;
+typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 
 // Disc sums of one output row (ring_disc_sum with 6 columns per lane): s0 is the ring slot of the row's Q index 0,
 // acc[t] the sum for the lane's column NCW lane + t (valid for DL <= lane < 64 - DL), ctr[t] that pixel's own value.
-// first (WIDE_PRIO): the wave's first row of the phase - its issue priority goes 3 -> 2 over that row and 1 -> 0 over the
-// second (CHAIN_PRIO, disc_wave_impl.hpp), so that the two chain waves of a SIMD advance together.
-template <int SIZE, int R, int LEAD>
-__device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[NCW], uint32_t (&ctr)[NCW], bool first) {
+// FIRST (WIDE_PRIO): the wave's first row of the phase - its issue priority goes 3 -> 2 over that row and 1 -> 0 over the
+// second (CHAIN_PRIO, disc_wave_impl.hpp), so that the two chain waves of a SIMD advance together.  A template argument,
+// so that no branch splits the chain: a DPP move and the add it feeds fold into one DPP add only within a basic block.
+template <int SIZE, int R, int GR, int LEAD, bool FIRST>
+__device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[NCW], uint32_t (&ctr)[NCW]) {
     using G = WGeo<SIZE>;
+    using BT = WBase<SIZE, GR>;
     constexpr int NR = G::NR;
     constexpr int DL = G::DL;
     constexpr int M = G::M;
     constexpr uint32_t PB = (uint32_t)G::W * 4;  // bytes per ring row
     constexpr uint32_t RB = (uint32_t)R * PB;
-    u32x4 top4[NR], bot4[NR];
-    u32x2w top2[NR], bot2[NR];
+    u32x2w top[NR][3], bot[NR][3];
     uint32_t cv[NR][NCW];
     uint32_t aR[NCW], aL[NCW];
-    const char* col4 = reinterpret_cast<const char*>(ring + lane * 4);
-    const char* col2 = reinterpret_cast<const char*>(ring + 256 + lane * 2);
-    const uint32_t b0 = (uint32_t)s0 * PB;
+    uint32_t vb[BT::T.nb];
+    lds_char* q = (lds_char*)ring;
+    const uint32_t b0 = (uint32_t)s0 * PB, lb = (uint32_t)lane * (NCW * 4);
     auto fetch = [&](int i) {
         const int r = G::S.order[i];
-        const uint32_t dt = (uint32_t)(G::T.run_hi[r] + 1 + M) * PB, db = (uint32_t)(G::T.run_lo[r] + M) * PB;
-        const uint32_t ot = min(b0 + dt, b0 + dt - RB), ob = min(b0 + db, b0 + db - RB);
-        top4[r] = *reinterpret_cast<const u32x4*>(col4 + ot);
-        top2[r] = *reinterpret_cast<const u32x2w*>(col2 + ot);
-        bot4[r] = *reinterpret_cast<const u32x4*>(col4 + ob);
-        bot2[r] = *reinterpret_cast<const u32x2w*>(col2 + ob);
+#pragma unroll
+        for (int b = 0; b < BT::T.nb; ++b)
+            if (BT::T.first[b] == i) {
+                const uint32_t d = b0 + (uint32_t)BT::T.kb[b] * PB;
+                vb[b] = lb + min(d, d - RB);  // the scalar wrap, then one vector add
+                asm("" : "+v"(vb[b]));        // (opaque: every read of the base keeps it and takes an immediate offset)
+            }
+        lds_char* pt = q + vb[BT::T.top_b[i]] + (uint32_t)(BT::T.top_k[i] - BT::T.kb[BT::T.top_b[i]]) * PB;
+        lds_char* pb = q + vb[BT::T.bot_b[i]] + (uint32_t)(BT::T.bot_k[i] - BT::T.kb[BT::T.bot_b[i]]) * PB;
+        // (volatile: three ds_read_b64, not merged into ds_read2_b64, which banks 32 wide and moves half as many bytes a cycle)
+#pragma unroll
+        for (int h = 0; h < 3; ++h) top[r][h] = *(lds_u32x2w*)(pt + 8 * h);
+#pragma unroll
+        for (int h = 0; h < 3; ++h) bot[r][h] = *(lds_u32x2w*)(pb + 8 * h);
     };
 #pragma unroll
     for (int i = 0; i < LEAD && i < NR; ++i) fetch(i);
 #if WIDE_PRIO
-    if (first) CHAIN_SETPRIO(3);
+    if (FIRST) CHAIN_SETPRIO(3);
     else CHAIN_SETPRIO(1);
 #endif
+    static_assert(DL >= 1, "the last step (D = 0) closes both chains");
 #pragma unroll
     for (int D = DL; D >= 0; --D) {
 #if WIDE_PRIO
         if (D == DL / 2) {
-            if (first) CHAIN_SETPRIO(2);
+            if (FIRST) CHAIN_SETPRIO(2);
             else CHAIN_SETPRIO(0);
         }
 #endif
@@ -170,9 +233,7 @@ __device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int 
                 if (j + LEAD < NR) fetch(j + LEAD);
                 RING_SB();
 #pragma unroll
-                for (int s = 0; s < 4; ++s) cv[r][s] = top4[r][s] - bot4[r][s];
-#pragma unroll
-                for (int s = 0; s < 2; ++s) cv[r][4 + s] = top2[r][s] - bot2[r][s];
+                for (int s = 0; s < NCW; ++s) cv[r][s] = top[r][s / 2][s % 2] - bot[r][s / 2][s % 2];
                 RING_SB();
             }
         }
@@ -198,6 +259,14 @@ __device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int 
             if (D == DL) {
                 aR[t] = pr;
                 aL[t] = pl;
+            } else if (D == 0) {
+                // the last step and the final aR + aL as one plain add and two DPP adds: hop(aR) + (hop_up(aL) + (pr + pl))
+                uint32_t own = anyr && anyl ? pr + pl : anyr ? pr : pl;
+                asm("" : "+v"(own));
+                own = hop_up(aL[t]) + own;
+                asm("" : "+v"(own));
+                aR[t] = hop(aR[t]) + own;  // the disc sum
+                asm("" : "+v"(aR[t]));     // (here, beside its DPP move, not sunk behind the caller's lane test)
             } else {
                 // (the lane's own part opaque: the DPP move folds into a two-operand add, see ring_disc_sum)
                 if (anyr) {
@@ -218,7 +287,7 @@ __device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int 
     }
 #pragma unroll
     for (int t = 0; t < NCW; ++t) {
-        acc[t] = aR[t] + aL[t];
+        acc[t] = aR[t];
         ctr[t] = cv[G::S.centre_run][t];
     }
 }
@@ -234,7 +303,7 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
     constexpr unsigned kHistMask = kWindow | kWindow * kFracOnly;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];
     uint32_t* Q = lds_u;
-    int* wflags = reinterpret_cast<int*>(Q + R * G::W);  // [2 parities][SW]: what each staging wave saw
+    int* wflags = reinterpret_cast<int*>(Q + (R + C::GR) * G::W);  // [2 parities][SW]: what each staging wave saw
 
     const int nb = (int)gridDim.x;
     const int vb = (nb & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (nb >> 3) + (int)(blockIdx.x >> 3);
@@ -247,7 +316,6 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
     const int rmin = max(0, p.in_row0), rmax = min(p.gny, p.in_row0 + p.in_rows);
     const bool stager = wave < SW;
     const int scol = 128 * wave + 2 * lane;  // a staging lane's first staged column (and the next one)
-    const int sdw0 = wide_dword_of_column(scol), sdw1 = wide_dword_of_column(scol + 1);
     int seen_tiles = 0, seen_frac = 0;
 
 #pragma unroll 1
@@ -295,8 +363,11 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                 run1 += (uint32_t)i1;
                 int sl = wslot + r;
                 sl = sl >= R ? sl - R : sl;
-                Q[sl * G::W + sdw0] = run0;
-                Q[sl * G::W + sdw1] = run1;
+                const u32x2w v2 = {run0, run1};
+                *reinterpret_cast<u32x2w*>(Q + sl * G::W + scol) = v2;
+                // the guard copy, in the same batch and so behind the same barrier as its source slot: a chain wave reads
+                // slot R + s only in a window that holds slot s, which the staging then does not write
+                if (sl < C::GR) *reinterpret_cast<u32x2w*>(Q + (sl + R) * G::W + scol) = v2;
             }
             // (in a batch without non-finite or absurd samples, x != (float)(int)x is a fractional part)
             const bool wild = __builtin_amdgcn_ballot_w64(amax >= kLimBits) != 0;
@@ -372,14 +443,16 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                 if (lane == 0) wflags[((ph + 1) & 1) * SW + wave] = seen;
                 load_batch(C::PRO + (ph + 1) * B, va);
             } else if (compute) {
-#pragma unroll 1
+                static_assert(C::RPW == 2, "two rows per chain wave: the first and the second priority pair");
+#pragma unroll
                 for (int k = 0; k < C::RPW; ++k) {
                     const int j = (wave - SW) * C::RPW + k;  // row of the phase
                     const int oy = oyA + j;
                     if (oy < p.out_row0 || oy >= p.out_row0 + p.out_rows) continue;
                     const int s0 = (C::PAD - 1 + ph * B + j) % R;  // slot of Q index 0 of the row's window
                     uint32_t acc[NCW], ctr[NCW];
-                    wide_disc_sum<SIZE, R, WIDE_LEAD>(Q, s0, lane, acc, ctr, k == 0);
+                    if (k == 0) wide_disc_sum<SIZE, R, C::GR, WIDE_LEAD, true>(Q, s0, lane, acc, ctr);
+                    else wide_disc_sum<SIZE, R, C::GR, WIDE_LEAD, false>(Q, s0, lane, acc, ctr);
                     if (lane_ok) {
                         float* o = p.tpi + (size_t)(oy - p.out_row0) * p.nx + ocol;
                         float out_t[NCW];
