@@ -111,11 +111,13 @@ int topo_amd_sync(void);
  *     topo_amd_raster_class_from_scan(block, in_rows, gny, nx, counts, range) declares the sum for the device rows
  *     [block, block + in_rows * nx) of a gny x nx raster - once per block the application holds (the share of fractional
  *     samples only picks which exact disc kernels run first: time, never bits).  A later call whose `in` pointer lies
- *     inside declared rows of a raster of the same shape takes that class.  A declaration lives exactly as long as the
- *     data it describes: it is dropped when the library writes or frees memory overlapping the rows (uploads, copies,
- *     memset, an output plane, topo_amd_free), by topo_amd_dem_changed, or by topo_amd_raster_class_set(..., large = -1,
- *     ...) (block == NULL: every declaration).  It is not a property of a thread or of the process: two rasters held in
- *     one process never see each other's class.
+ *     inside declared rows of a raster of the same shape takes that class.  Blocks may overlap (views of one buffer, each
+ *     with its ghost rows): declarations of the same shape and class keep one entry per block, in any order; one of
+ *     another shape or class replaces every declaration it overlaps, one of the same rows replaces their declaration.
+ *     A declaration lives exactly as long as the data it describes: it is dropped when the library writes or frees
+ *     memory overlapping the rows (uploads, copies, memset, an output plane, topo_amd_free), by topo_amd_dem_changed, or
+ *     by topo_amd_raster_class_set(..., large = -1, ...) (block == NULL: every declaration).  It is not a property of a
+ *     thread or of the process: two rasters held in one process never see each other's class.
  *   - the topo_amd_shard_* calls declare the class of their shard THEMSELVES at the first call on a buffer nothing is
  *     declared for (topo_amd_shard_classify: the scans of all ranks, added up by an all-reduce - collective like the
  *     calls themselves), so every shard takes the single GPU's kernels without the application doing anything.

@@ -152,20 +152,24 @@ def test_wide_relief_and_large_values_are_exact(name, size):
     assert np.array_equal(topo.std(dem, size), s.astype(np.float64))
 
 
+def small_value_raster(kind):
+    """300 x 384 rasters of small or narrow values: "unit_range", "kilometres", "constant_fraction" or "flat"."""
+    base = orc.synthetic_dem(300, 384, seed=21, integer=False)
+    if kind == "unit_range":
+        return ((base - base.min()) / (base.max() - base.min())).astype(np.float32)
+    if kind == "kilometres":
+        return (base / 1000.0).astype(np.float32)
+    if kind == "constant_fraction":
+        return (np.rint(base) + 0.002).astype(np.float32)
+    return (500.0 + 0.01 * (base - base.mean())).astype(np.float32)
+
+
 @pytest.mark.parametrize("kind", ["unit_range", "kilometres", "constant_fraction", "flat"])
 def test_scaled_tpi_on_rasters_of_small_values(kind):
     """the scaled one-chain route quantised every raster to 2^-8, whatever its values.  The unit now
     follows the raster's value range (2^-8 ... 2^-16), so a normalised surface or a DEM in kilometres keeps 1e-4 of ITS
     range, and a constant fractional offset stays inside the bound."""
-    base = orc.synthetic_dem(300, 384, seed=21, integer=False)
-    if kind == "unit_range":
-        dem = ((base - base.min()) / (base.max() - base.min())).astype(np.float32)
-    elif kind == "kilometres":
-        dem = (base / 1000.0).astype(np.float32)
-    elif kind == "constant_fraction":
-        dem = (np.rint(base) + 0.002).astype(np.float32)
-    else:
-        dem = (500.0 + 0.01 * (base - base.mean())).astype(np.float32)
+    dem = small_value_raster(kind)
     for size in (19, 67):
         got = topo.tpi(dem, size)
         want = orc.tpi_exact(dem, size)

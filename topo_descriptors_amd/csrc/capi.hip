@@ -116,9 +116,11 @@ int memo_slot(const Block& b, bool create) {
 }
 // What was declared for partial row blocks (topo_amd_raster_class_set / _from_scan / topo_amd_shard_classify): keyed by the
 // device rows the declaration was made for and the shape of the raster they belong to.  A call's block finds its class
-// when its first row lies inside a declared range of a raster of the same shape.  Dropped like the memo: whenever the
-// library writes or frees memory that overlaps the range, by topo_amd_dem_changed, and by a withdrawal.  Nothing here
-// belongs to a thread or outlives its memory: two rasters in one process cannot inherit each other's class.
+// when its first row lies inside a declared range of a raster of the same shape.  Declarations of one raster shape and
+// class may overlap (row blocks of one buffer, each with its ghost rows: one entry per block); a declaration replaces
+// the entries it overlaps that have another shape or class, and the entry of exactly its rows.  Dropped like the memo:
+// whenever the library writes or frees memory that overlaps the range, by topo_amd_dem_changed, and by a withdrawal.
+// Nothing here belongs to a thread or outlives its memory: two rasters in one process cannot inherit each other's class.
 struct Declared {
     uintptr_t lo = 0, hi = 0;  // [lo, hi): the device rows
     int gny = 0, nx = 0;
@@ -146,9 +148,16 @@ bool declared_class(const Block& b, RasterClass* out) {
 void declare_class(const float* block, int in_rows, int gny, int nx, const RasterClass& cls) {
     std::lock_guard<std::mutex> lock(g_memo_mu);
     const uintptr_t lo = (uintptr_t)block, hi = lo + (size_t)in_rows * nx * sizeof(float);
-    // a declaration replaces whatever was declared for overlapping memory
-    g_declared.erase(std::remove_if(g_declared.begin(), g_declared.end(), [&](const Declared& e) { return e.lo < hi && lo < e.hi; }),
-                     g_declared.end());
+    // a declaration replaces what was declared for overlapping memory of a raster of another shape or with another class,
+    // and a declaration of exactly these rows; overlapping blocks of the same raster and class (row blocks of one buffer,
+    // each with its ghost rows) keep their own entries, so a later write drops only those overlapping the written rows
+    const auto replaced = [&](const Declared& e) {
+        if (!(e.lo < hi && lo < e.hi)) return false;
+        const bool same = e.gny == gny && e.nx == nx && e.cls.large == cls.large && e.cls.lo == cls.lo && e.cls.hi == cls.hi &&
+                          e.cls.frac_share == cls.frac_share;
+        return !same || (e.lo == lo && e.hi == hi);
+    };
+    g_declared.erase(std::remove_if(g_declared.begin(), g_declared.end(), replaced), g_declared.end());
     if (g_declared.size() >= kMaxDeclared) {
         auto oldest = std::min_element(g_declared.begin(), g_declared.end(), [](const Declared& x, const Declared& y) { return x.used < y.used; });
         g_declared.erase(oldest);

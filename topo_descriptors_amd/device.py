@@ -82,7 +82,9 @@ class RasterScan:
         return self
 
     def declare(self, *blocks):
-        """Declare the class added up so far for the device rows of each :class:`Block` in ``blocks``."""
+        """Declare the class added up so far for the device rows of each :class:`Block` in ``blocks``.  The blocks may
+        overlap (views of one buffer with their ghost rows): each keeps its declaration, whatever the order; a later
+        declaration of another class or raster shape replaces the declarations it overlaps."""
         if not blocks:
             raise ValueError("RasterScan.declare: name the blocks the class is declared for (it is keyed by their memory)")
         for blk in blocks:
