@@ -244,11 +244,14 @@ int topo_amd_sx_multi_dev(const float* in, int in_rows, int in_row0, int gny, in
 /* Valley / ridge index (replaces the angle loop of topo.valley_ridge, topo.py:431-447).
  * The host builds the kernels exactly as the reference does (V / U profiles topo.py:456-492,
  * quadratic-spline rotation and re-normalisation :515-525) and hands over, for each of
- * n_angles angles, n_planes (1..4) 2-D kernels of side ksize[a]: the sums of neighbouring
- * kernel planes that the reference's 3-D "same" convolution of the broadcast DEM applies
- * (DESIGN.md), flipped in both axes so that the device evaluates a correlation.  taps: HOST
- * float32, angle after angle, ksize[a]^2 taps in row-major order, 4 floats per tap (one per
- * plane, unused ones 0).  angles: HOST float32, the value stored in dir_out for each angle.
+ * n_angles angles, n_planes (1..TOPO_AMD_VALLEY_MAX_PLANES, one per flat fraction) 2-D kernels
+ * of side ksize[a]: the sums of neighbouring kernel planes that the reference's 3-D "same"
+ * convolution of the broadcast DEM applies, flipped in both axes so that the device
+ * evaluates a correlation.  taps: HOST float32, angle after angle, ksize[a]^2 taps in row-major
+ * order, 4 ceil(n_planes / 4) floats per tap: group g holds planes 4g .. 4g+3, unused slots 0
+ * (4 floats for up to 4 planes).  The host tables grow with ceil(n_planes / 4): at 1001 px the
+ * tables of 3 planes already take ~5.8 GB, those of 5 to 8 planes twice that.  More planes than
+ * TOPO_AMD_VALLEY_MAX_PLANES: TOPO_AMD_EINVAL.  angles: HOST float32, the value stored in dir_out for each angle.
  * mean / stdev: the DEM is normalised as (x - mean) / stdev in float32 while it is read
  * (topo.py:427); topo_amd_mean_std_dev computes them for a device-resident DEM.
  * norm_out = max over angles and planes, clipped at 0; dir_out = first angle reaching it.
@@ -264,7 +267,10 @@ int topo_amd_sx_multi_dev(const float* in, int in_rows, int in_row0, int gny, in
  * reference's signal.convolve.  The first two: a pixel whose kernel footprint holds a
  * non-finite sample is evaluated tap by tap in both, row blocks give the single block's bits.
  * FFT: same contract (1e-4 of the range), but a NaN in the block reaches every output and
- * row blocks agree to rounding instead of bit for bit.                                      */
+ * row blocks agree to rounding instead of bit for bit.  More than 4 planes: the first two run
+ * the planes in groups of four and merge the groups' unclipped maxima (the larger value, then
+ * the earlier angle index), the FFT evaluates all planes in one pass; same contract.         */
+#define TOPO_AMD_VALLEY_MAX_PLANES 16
 int topo_amd_valley_ridge_dev(const float* in, int in_rows, int in_row0, int gny, int nx,
                               const float* taps, const int32_t* ksize, const float* angles,
                               int n_angles, int n_planes, double mean, double stdev,
@@ -273,7 +279,8 @@ int topo_amd_valley_ridge_dev(const float* in, int in_rows, int in_row0, int gny
  * 1 matrix pipe, 2 FFT; + 4: the matrix-pipe pass was followed by the tap-by-tap kernel over the tiles in which it met
  * non-finite samples (launched whenever the matrix pipe is used; it returns at once in tiles that are not flagged);
  * + 8: the matrix pipe ran over pairs of opposite cells (point-symmetric tables); + 16: with the pixel operands streamed
- * in chunks (more than 240 pairs: kernels of 19 px and more).                                                            */
+ * in chunks (more than 240 pairs: kernels of 19 px and more); + 32: more than 4 planes, run in groups of four through
+ * those kernels (the codes of the groups OR-ed; the FFT takes all planes in one pass and reports 2).                    */
 int topo_amd_valley_route(int* route);
 /* Which kernel the calling thread's last TPI / STD disc call (topo_amd_tpi_std_dev and the calls built on it) finished
  * its whole-metre tiles with (for tests and diagnostics): 1 the wide ring (TPI alone, 67 px, a single block of a

@@ -87,7 +87,8 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
-constexpr int kWorkspaces = 14;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard)
+constexpr int kWorkspaces = 15;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
+                                 // 14: a valley plane group's outputs)
 constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;
@@ -212,9 +213,19 @@ int launch_synth(float* out, int rows, int row0, int nx, uint32_t seed, bool int
 // nearest valid sample along x (fill.hip): output rows [out_row0, out_row0 + out_rows) of the block; xs: device double[nx]
 // (nullptr: the column index); out may be the block's own rows (in place); missing: uint8 plane or nullptr
 int launch_fill_na(const Block& b, const double* xs, bool ascending, bool use_thresh, float thresh, float* out, uint8_t* missing);
-// valley / ridge index (valley.hip): taps = per angle ksize^2 x 4 floats (plane sums, flipped)
-// the same by FFT, for kernels of any size (valley_fft.hip)
-int launch_valley_ridge_fft(const Block& b, const float* taps, const int32_t* ksize, const float* angles,
+// valley / ridge index (valley.hip): taps = per angle ksize^2 x 4 ceil(n_planes / 4) floats (plane sums, flipped)
+// The kernels evaluate at most four planes at a time; a call with more runs its planes in groups of four (valley.hip).  One
+// evaluation's view of the call's tables:
+struct VrGroup {
+    int stride = 4;      // floats per tap: 4 ceil(planes of the call / 4)
+    int p0 = 0;          // the evaluation's first plane
+    int n_live = 1;      // planes of the call: a cell with a tap in any of them is in every group's window (the same pixels
+                         // meet a non-finite sample in every group, and the same pixels go to the tap-by-tap pass)
+    float floor = 0.0f;  // norm_out = max(best, floor): 0 is the clip; -inf keeps the best unclipped (groups)
+    float mark = -1.0f;  // what the matrix pipe leaves in norm_out for the tap-by-tap pass (never a value it stores)
+};
+// the same by FFT, for kernels of any size, all planes in one pass (valley_fft.hip)
+int launch_valley_ridge_fft(const Block& b, const float* taps, int stride, const int32_t* ksize, const float* angles,
                             int n_angles, int n_planes, int kmax, double mean, double stdev, float* norm_out,
                             float* dir_out);
 void valley_fft_release();  // destroys the cached FFT plans (topo_amd_shutdown)
@@ -223,12 +234,12 @@ void note_tpi_route(int route);     // what topo_amd_tpi_route reports for the c
 void note_valley_route(int route);  // what topo_amd_valley_route reports for the calling thread (capi.hip)
 // the same on the matrix pipe for rotated kernels of up to kValleyMfmaMaxKernel cells a side with at most 240 cells that hold a
 // tap at any angle (valley_mfma.hip; *done = 0: not such a case, nothing launched); leaves the pixels it cannot do marked
-// norm = -1 and their tiles (kValleyMfmaTileRows x 64, anchored at out_row0) flagged
+// norm = g.mark and their tiles (kValleyMfmaTileRows x 64, anchored at out_row0) flagged.  n_planes (1..4): planes g.p0 ...
 constexpr int kValleyMfmaMaxKernel = 25;     // ... with a pixel tile's operands in registers
 constexpr int kValleyStreamMaxKernel = 120;  // ... folded with the operands streamed (point-symmetric tables)
 constexpr int kValleyMfmaTileRows = 32;
-int launch_valley_ridge_mfma(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles,
-                             int n_planes, int kmax, double mean, double stdev, float* norm_out, float* dir_out,
+int launch_valley_ridge_mfma(const Block& b, const float* taps, const VrGroup& g, const int32_t* ksize, const float* angles,
+                             int n_angles, int n_planes, int kmax, double mean, double stdev, float* norm_out, float* dir_out,
                              const int** flags_out, int* flag_cols, int* done);
 int launch_mean_std(const float* in, size_t count, double* mean, double* stdev);
 int launch_moments(const float* in, size_t count, double pivot, bool pivot_is_first_sample, double* sum, double* sumsq);

@@ -24,6 +24,9 @@
 // 5 x as fast); this kernel then follows it in "repair" mode over the tiles that one flagged and rewrites exactly the pixels
 // it marked (norm = -1: a non-finite sample in the kernel footprint) - and remains the evaluation of everything between 19
 // and 63 px, and the reference of the matrix-pipe kernels' tests (TOPO_AMD_VALLEY_MFMA_MAX_KERNEL=0).
+// More than four planes (flat fractions): the kernels are built for 1 to 4; the launcher runs the planes in groups of four
+// through them and merges the groups (launch_valley_ridge below).  Grouping does fewer matrix-pipe products than wider
+// instantiations would: 6 planes take 23 + 12 filter tiles of 180 angles as a group of 4 and one of 2, 45 as one of 6.
 #include "common.hpp"
 
 #include <algorithm>
@@ -57,7 +60,8 @@ struct VrArgs {
     int out_row0, out_rows;
     int kmax, stride, rows_l, cols_l;
     float mean, stdev;
-    const int* repair;  // not NULL: behind valley_mfma.hip - only the tiles it flagged, and in them only the pixels it marked norm = -1
+    float floor, mark;  // VrGroup (common.hpp): norm = max(best, floor); the mark valley_mfma.hip leaves on the pixels it hands over
+    const int* repair;  // not NULL: behind valley_mfma.hip - only the tiles it flagged, and in them only the pixels it marked norm = mark
     int repair_cols;
 };
 
@@ -139,8 +143,8 @@ __global__ __launch_bounds__(kThreads) void valley_ridge_kernel(VrArgs p) {
         const int oy = oy0 + wave + 4 * r;
         if (oy >= p.out_row0 + p.out_rows) continue;
         const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
-        if (p.repair != nullptr && p.norm[o] != -1.0f) continue;
-        p.norm[o] = fmaxf(best[r], 0.0f);  // clip(min=0), topo.py:446
+        if (p.repair != nullptr && p.norm[o] != p.mark) continue;
+        p.norm[o] = fmaxf(best[r], p.floor);  // clip(min=0), topo.py:446
         p.dir[o] = best_angle[r];
     }
 }
@@ -152,6 +156,125 @@ int launch_np(const VrArgs& a, dim3 grid, size_t lds) {
     hipLaunchKernelGGL(valley_ridge_kernel<NP>, grid, dim3(kThreads), lds, ctx().compute, a);
     TOPO_HIP(hipGetLastError());
     return TOPO_AMD_OK;
+}
+
+// More than four planes: the running result of the groups so far (best unclipped, the index of its angle as a float) takes a
+// group's where that one is larger, or equal at an earlier angle - the rule by which valley_mfma.hip merges its canvas classes
+// and lane halves - so the result is the maximum over all planes and the first angle, in the order of `angles`, that reaches it.
+__global__ __launch_bounds__(kThreads) void merge_groups_kernel(const float* gv, const float* gi, float* best, float* index,
+                                                                size_t n) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float v = gv[i], b = best[i];
+    if (v > b || (v == b && gi[i] < index[i])) {
+        best[i] = v;
+        index[i] = gi[i];
+    }
+}
+
+// after the last group: the clip, and the angle of the index (0 where no angle ever beat -inf, like the one-pass kernels)
+__global__ __launch_bounds__(kThreads) void finish_groups_kernel(float* norm, float* dir, const float* angles, int n_angles,
+                                                                 size_t n) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float v = norm[i];
+    norm[i] = fmaxf(v, 0.0f);  // clip(min=0), topo.py:446
+    dir[i] = v > -INFINITY ? angles[min(max((int)dir[i], 0), n_angles - 1)] : 0.0f;
+}
+
+// One evaluation of planes g.p0 .. g.p0 + n_planes - 1 (at most four): the matrix pipe, followed by the tap-by-tap kernel over the
+// tiles it flagged, or the tap-by-tap kernel alone.  *route: topo_amd_valley_route's code; 2: neither takes it, it is the FFT's
+// (nothing launched).
+int valley_pass(const Block& b, const float* taps, const VrGroup& g, const int32_t* ksize, const float* angles, int n_angles,
+                int n_planes, int kmax, double mean, double stdev, float* norm_out, float* dir_out, int* route) {
+    VrArgs a{};
+    a.in = b.in;
+    a.norm = norm_out;
+    a.dir = dir_out;
+    a.n_angles = n_angles;
+    a.in_rows = b.in_rows;
+    a.in_row0 = b.in_row0;
+    a.gny = b.gny;
+    a.nx = b.nx;
+    a.out_row0 = b.out_row0;
+    a.out_rows = b.out_rows;
+    a.kmax = kmax;
+    a.rows_l = kTileH + kmax - 1;
+    a.cols_l = kTileW + kmax - 1;
+    a.stride = a.cols_l | 1;
+    a.mean = (float)mean;
+    a.stdev = (float)stdev;
+    a.floor = g.floor;
+    a.mark = g.mark;
+    const size_t lds = (size_t)a.rows_l * a.stride * sizeof(float);
+    // Which evaluation.  The matrix pipe (valley_mfma.hip) for everything it takes: rotated kernels of up to 120 cells a side when
+    // the tables are point-symmetric, of up to 25 otherwise - this kernel then only visits the tiles in which that one met a
+    // non-finite sample.  Else, large kernels by FFT (valley_fft.hip), whose cost does not depend on the kernel size: from 64
+    // cells a side, or from TOPO_AMD_VALLEY_FFT_MIN_KERNEL - which, when set, also takes those kernels away from the matrix pipe
+    // (the tests' way to the FFT route) - and whatever this kernel cannot stage.
+    const char* e = std::getenv("TOPO_AMD_VALLEY_FFT_MIN_KERNEL");
+    const bool fft_pinned = e && *e;
+    const int fft_from = fft_pinned ? std::atoi(e) : kValleyFftFrom;
+    const bool stageable = lds <= 160 * 1024;
+    e = std::getenv("TOPO_AMD_VALLEY_MFMA_MAX_KERNEL");
+    const int mfma_upto = e && *e ? std::min(std::atoi(e), kValleyStreamMaxKernel) : kValleyStreamMaxKernel;
+    int done = 0;
+    if (kmax <= mfma_upto && stageable && !(fft_pinned && kmax >= fft_from))
+        TOPO_TRY(launch_valley_ridge_mfma(b, taps, g, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out,
+                                          &a.repair, &a.repair_cols, &done));
+    if (!done) a.repair = nullptr;
+    if (!done && (kmax >= fft_from || !stageable)) {
+        *route = 2;
+        return TOPO_AMD_OK;
+    }
+    *route = done ? 1 + 4 + (done >= 2 ? 8 : 0) + (done == 3 ? 16 : 0) : 0;
+    // compress: the non-zero taps of each angle, with their offset in the LDS tile (smaller kernels
+    // sit centred inside the reach staged for the largest one)
+    size_t dense = 0;
+    for (int ang = 0; ang < n_angles; ++ang) dense += (size_t)ksize[ang] * ksize[ang];
+    std::vector<int> meta((size_t)2 * n_angles);
+    std::vector<float> wlist;
+    std::vector<int> olist;
+    wlist.reserve(dense * 2);
+    olist.reserve(dense / 2);
+    const float* src = taps;
+    for (int ang = 0; ang < n_angles; ++ang) {
+        const int ks = ksize[ang];
+        const int shift = kmax / 2 - ks / 2;
+        meta[2 * ang + 1] = (int)olist.size();
+        for (int ky = 0; ky < ks; ++ky) {
+            for (int kx = 0; kx < ks; ++kx, src += g.stride) {
+                bool any = false;  // (a tap of any plane of the call: every group evaluates the same window)
+                for (int q = 0; q < g.n_live; ++q) any = any || src[q] != 0.0f;
+                if (!any) continue;
+                wlist.insert(wlist.end(), src + g.p0, src + g.p0 + 4);
+                olist.push_back((ky + shift) * a.stride + kx + shift);
+            }
+        }
+        meta[2 * ang] = (int)olist.size() - meta[2 * ang + 1];
+    }
+    if (olist.empty()) {  // keep the tables non-empty for the uploads
+        wlist.assign(4, 0.0f);
+        olist.assign(1, 0);
+    }
+    void *d_taps = nullptr, *d_off = nullptr, *d_meta = nullptr, *d_angles = nullptr;
+    TOPO_TRY(upload_table(0, wlist.data(), wlist.size() * sizeof(float), &d_taps));
+    TOPO_TRY(upload_table(3, olist.data(), olist.size() * sizeof(int), &d_off));
+    TOPO_TRY(upload_table(1, meta.data(), meta.size() * sizeof(int), &d_meta));
+    TOPO_TRY(upload_table(2, angles, (size_t)n_angles * sizeof(float), &d_angles));
+    a.taps = (const tap4*)d_taps;
+    a.tap_off = (const int*)d_off;
+    a.meta = (const int*)d_meta;
+    a.angles = (const float*)d_angles;
+    dim3 grid((b.nx + kTileW - 1) / kTileW, (b.out_rows + kTileH - 1) / kTileH);
+    switch (n_planes) {  // (never a narrower instantiation than the pass has planes)
+        case 1: return launch_np<1>(a, grid, lds);
+        case 2: return launch_np<2>(a, grid, lds);
+        case 3: return launch_np<3>(a, grid, lds);
+        case 4: return launch_np<4>(a, grid, lds);
+    }
+    TOPO_REQUIRE(false, "valley_ridge: %d planes in one pass (1 to 4 are built)", n_planes);
+    return TOPO_AMD_EINVAL;
 }
 
 }  // namespace
@@ -235,7 +358,8 @@ int valley_ridge_reach(const int32_t* ksize, int n_angles, int* above, int* belo
 
 int launch_valley_ridge(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles,
                         int n_planes, double mean, double stdev, float* norm_out, float* dir_out) {
-    TOPO_REQUIRE(n_planes >= 1 && n_planes <= 4, "valley_ridge: %d kernel planes (1 to 4 are built)", n_planes);
+    TOPO_REQUIRE(n_planes >= 1 && n_planes <= TOPO_AMD_VALLEY_MAX_PLANES, "valley_ridge: %d kernel planes (1 to %d are supported)",
+                 n_planes, TOPO_AMD_VALLEY_MAX_PLANES);
     TOPO_REQUIRE(n_angles >= 1, "valley_ridge: no angles");
     TOPO_REQUIRE(stdev > 0.0 && stdev == stdev && mean == mean, "valley_ridge: mean %g / std %g of the DEM", mean, stdev);
     size_t dense = 0;
@@ -246,88 +370,57 @@ int launch_valley_ridge(const Block& b, const float* taps, const int32_t* ksize,
     }
     int above = 0, below = 0;
     const int kmax = valley_ridge_reach(ksize, n_angles, &above, &below);
-    VrArgs a{};
-    a.in = b.in;
-    a.norm = norm_out;
-    a.dir = dir_out;
-    a.n_angles = n_angles;
-    a.in_rows = b.in_rows;
-    a.in_row0 = b.in_row0;
-    a.gny = b.gny;
-    a.nx = b.nx;
-    a.out_row0 = b.out_row0;
-    a.out_rows = b.out_rows;
-    a.kmax = kmax;
-    a.rows_l = kTileH + kmax - 1;
-    a.cols_l = kTileW + kmax - 1;
-    a.stride = a.cols_l | 1;
-    a.mean = (float)mean;
-    a.stdev = (float)stdev;
-    const size_t lds = (size_t)a.rows_l * a.stride * sizeof(float);
-    // Which evaluation.  The matrix pipe (valley_mfma.hip) for everything it takes: rotated kernels of up to 120 cells a side when
-    // the tables are point-symmetric, of up to 25 otherwise - this kernel then only visits the tiles in which that one met a
-    // non-finite sample.  Else, large kernels by FFT (valley_fft.hip), whose cost does not depend on the kernel size: from 64
-    // cells a side, or from TOPO_AMD_VALLEY_FFT_MIN_KERNEL - which, when set, also takes those kernels away from the matrix pipe
-    // (the tests' way to the FFT route) - and whatever this kernel cannot stage.
-    const char* e = std::getenv("TOPO_AMD_VALLEY_FFT_MIN_KERNEL");
-    const bool fft_pinned = e && *e;
-    const int fft_from = fft_pinned ? std::atoi(e) : kValleyFftFrom;
-    const bool stageable = lds <= 160 * 1024;
-    e = std::getenv("TOPO_AMD_VALLEY_MFMA_MAX_KERNEL");
-    const int mfma_upto = e && *e ? std::min(std::atoi(e), kValleyStreamMaxKernel) : kValleyStreamMaxKernel;
-    int done = 0;
-    if (kmax <= mfma_upto && stageable && !(fft_pinned && kmax >= fft_from))
-        TOPO_TRY(launch_valley_ridge_mfma(b, taps, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out,
-                                          &a.repair, &a.repair_cols, &done));
-    if (!done) a.repair = nullptr;
-    if (!done && (kmax >= fft_from || !stageable)) {
-        note_valley_route(2);
-        return launch_valley_ridge_fft(b, taps, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out);
+    const int n_groups = (n_planes + 3) / 4;
+    VrGroup g;
+    g.stride = 4 * n_groups;
+    g.n_live = n_planes;
+    int route = 0;
+    if (n_groups == 1) {
+        TOPO_TRY(valley_pass(b, taps, g, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out, &route));
+        note_valley_route(route);
+        if (route == 2)
+            return launch_valley_ridge_fft(b, taps, g.stride, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out);
+        return TOPO_AMD_OK;
     }
-    note_valley_route(done ? 1 + 4 + (done >= 2 ? 8 : 0) + (done == 3 ? 16 : 0) : 0);
-    // compress: the non-zero taps of each angle, with their offset in the LDS tile (smaller kernels
-    // sit centred inside the reach staged for the largest one)
-    std::vector<int> meta((size_t)2 * n_angles);
-    std::vector<float> wlist;
-    std::vector<int> olist;
-    wlist.reserve(dense * 2);
-    olist.reserve(dense / 2);
-    const float* src = taps;
-    for (int ang = 0; ang < n_angles; ++ang) {
-        const int ks = ksize[ang];
-        const int shift = kmax / 2 - ks / 2;
-        meta[2 * ang + 1] = (int)olist.size();
-        for (int ky = 0; ky < ks; ++ky) {
-            for (int kx = 0; kx < ks; ++kx, src += 4) {
-                bool any = false;
-                for (int q = 0; q < n_planes; ++q) any = any || src[q] != 0.0f;
-                if (!any) continue;
-                wlist.insert(wlist.end(), src, src + 4);
-                olist.push_back((ky + shift) * a.stride + kx + shift);
-            }
+    // More than four planes: the groups of four run one after the other through the kernels above with the angles' INDICES as
+    // the values to store and the best left unclipped (the mark of a pixel for the tap-by-tap pass is then -inf, which no
+    // finite best is); the first group writes the outputs, each further one its own plane pair, merged into them; the clip and
+    // the angles at the end.  The groups' windows are the same (VrGroup::n_live), so the matrix pipe hands the same pixels to
+    // the tap-by-tap kernel in every group.  The FFT evaluates all planes in one pass.
+    const size_t out_n = (size_t)b.out_rows * b.nx;
+    std::vector<float> index((size_t)n_angles);
+    for (int i = 0; i < n_angles; ++i) index[i] = (float)i;
+    g.floor = -INFINITY;
+    g.mark = -INFINITY;
+    void* d_group = nullptr;
+    TOPO_TRY(workspace(14, 2 * out_n * sizeof(float), &d_group));
+    float* gv = (float*)d_group;
+    float* gi = gv + out_n;
+    const dim3 grid1((unsigned)((out_n + kThreads - 1) / kThreads));
+    for (int grp = 0; grp < n_groups; ++grp) {
+        g.p0 = 4 * grp;
+        int r = 0;
+        TOPO_TRY(valley_pass(b, taps, g, ksize, index.data(), n_angles, std::min(4, n_planes - g.p0), kmax, mean, stdev,
+                             grp == 0 ? norm_out : gv, grp == 0 ? dir_out : gi, &r));
+        if (r == 2) {  // (the tables' size alone decides it: the first group, or none)
+            TOPO_REQUIRE(grp == 0, "valley_ridge: plane group %d without a route", grp);
+            note_valley_route(2);
+            return launch_valley_ridge_fft(b, taps, g.stride, ksize, angles, n_angles, n_planes, kmax, mean, stdev, norm_out, dir_out);
         }
-        meta[2 * ang] = (int)olist.size() - meta[2 * ang + 1];
+        route |= r;
+        if (grp > 0) {
+            hipLaunchKernelGGL(merge_groups_kernel, grid1, dim3(kThreads), 0, ctx().compute, (const float*)gv, (const float*)gi,
+                               norm_out, dir_out, out_n);
+            TOPO_HIP(hipGetLastError());
+        }
     }
-    if (olist.empty()) {  // keep the tables non-empty for the uploads
-        wlist.assign(4, 0.0f);
-        olist.assign(1, 0);
-    }
-    void *d_taps = nullptr, *d_off = nullptr, *d_meta = nullptr, *d_angles = nullptr;
-    TOPO_TRY(upload_table(0, wlist.data(), wlist.size() * sizeof(float), &d_taps));
-    TOPO_TRY(upload_table(3, olist.data(), olist.size() * sizeof(int), &d_off));
-    TOPO_TRY(upload_table(1, meta.data(), meta.size() * sizeof(int), &d_meta));
+    note_valley_route(route + 32);
+    void* d_angles = nullptr;
     TOPO_TRY(upload_table(2, angles, (size_t)n_angles * sizeof(float), &d_angles));
-    a.taps = (const tap4*)d_taps;
-    a.tap_off = (const int*)d_off;
-    a.meta = (const int*)d_meta;
-    a.angles = (const float*)d_angles;
-    dim3 grid((b.nx + kTileW - 1) / kTileW, (b.out_rows + kTileH - 1) / kTileH);
-    switch (n_planes) {
-        case 1: return launch_np<1>(a, grid, lds);
-        case 2: return launch_np<2>(a, grid, lds);
-        case 3: return launch_np<3>(a, grid, lds);
-        default: return launch_np<4>(a, grid, lds);
-    }
+    hipLaunchKernelGGL(finish_groups_kernel, grid1, dim3(kThreads), 0, ctx().compute, norm_out, dir_out, (const float*)d_angles,
+                       n_angles, out_n);
+    TOPO_HIP(hipGetLastError());
+    return TOPO_AMD_OK;
 }
 
 }  // namespace topo

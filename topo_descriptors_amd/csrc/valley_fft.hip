@@ -94,14 +94,14 @@ __global__ __launch_bounds__(kThreads) void normalise_pad_kernel(const float* in
     z[(size_t)y * Q + x] = v;
 }
 
-// plane `q` of a kernel of side ks (taps: ks*ks float4) at minus its tap offsets, or zeros there again
-__global__ __launch_bounds__(kThreads) void scatter_kernel(const float* taps, int ks, int q, bool clear, float* k,
+// plane `q` of a kernel of side ks (taps: ks*ks taps of `stride` floats) at minus its tap offsets, or zeros there again
+__global__ __launch_bounds__(kThreads) void scatter_kernel(const float* taps, int stride, int ks, int q, bool clear, float* k,
                                                            int P, int Q) {
     const int idx = blockIdx.x * kThreads + threadIdx.x;
     if (idx >= ks * ks) return;
     const int dy = idx / ks - ks / 2, dx = idx % ks - ks / 2;
     const int r = dy > 0 ? P - dy : -dy, c = dx > 0 ? Q - dx : -dx;
-    k[(size_t)r * Q + c] = clear ? 0.0f : taps[(size_t)idx * 4 + q];
+    k[(size_t)r * Q + c] = clear ? 0.0f : taps[(size_t)idx * stride + q];
 }
 
 __global__ __launch_bounds__(kThreads) void spectrum_product_kernel(const float2* f, float2* g, size_t n, float scale) {
@@ -150,7 +150,7 @@ void valley_fft_release() {
     plan_cache().clear();
 }
 
-int launch_valley_ridge_fft(const Block& b, const float* taps, const int32_t* ksize, const float* angles,
+int launch_valley_ridge_fft(const Block& b, const float* taps, int stride, const int32_t* ksize, const float* angles,
                             int n_angles, int n_planes, int kmax, double mean, double stdev, float* norm_out,
                             float* dir_out) {
     Context& c = ctx();
@@ -168,7 +168,7 @@ int launch_valley_ridge_fft(const Block& b, const float* taps, const int32_t* ks
     TOPO_TRY(workspace(5, cplx_n * sizeof(float2), &g));
     TOPO_TRY(workspace(6, real_n * sizeof(float), &kimg));
     TOPO_TRY(workspace(7, real_n * sizeof(float), &resp));
-    TOPO_TRY(workspace(1, (size_t)kmax * kmax * 4 * sizeof(float), &d_taps));
+    TOPO_TRY(workspace(1, (size_t)kmax * kmax * stride * sizeof(float), &d_taps));
     TOPO_TRY(workspace(2, out_n * sizeof(float), &tmp));
 
     // Z goes through `resp` (free until the first inverse transform)
@@ -189,14 +189,14 @@ int launch_valley_ridge_fft(const Block& b, const float* taps, const int32_t* ks
         const int ks = ksize[a];
         const size_t ntap = (size_t)ks * ks;
         // the previous angle's kernels are done with d_taps: everything runs on one stream
-        TOPO_HIP(hipMemcpyAsync(d_taps, src, ntap * 4 * sizeof(float), hipMemcpyHostToDevice, c.compute));
-        src += ntap * 4;
+        TOPO_HIP(hipMemcpyAsync(d_taps, src, ntap * stride * sizeof(float), hipMemcpyHostToDevice, c.compute));
+        src += ntap * stride;
         for (int q = 0; q < n_planes; ++q) {
-            hipLaunchKernelGGL(scatter_kernel, grid1(ntap), dim3(kThreads), 0, c.compute, (const float*)d_taps, ks, q,
+            hipLaunchKernelGGL(scatter_kernel, grid1(ntap), dim3(kThreads), 0, c.compute, (const float*)d_taps, stride, ks, q,
                                false, (float*)kimg, P, Q);
             TOPO_HIP(hipGetLastError());
             TOPO_FFT(hipfftExecR2C(plans.fwd, (hipfftReal*)kimg, (hipfftComplex*)g));
-            hipLaunchKernelGGL(scatter_kernel, grid1(ntap), dim3(kThreads), 0, c.compute, (const float*)d_taps, ks, q,
+            hipLaunchKernelGGL(scatter_kernel, grid1(ntap), dim3(kThreads), 0, c.compute, (const float*)d_taps, stride, ks, q,
                                true, (float*)kimg, P, Q);
             hipLaunchKernelGGL(spectrum_product_kernel, grid1(cplx_n), dim3(kThreads), 0, c.compute, (const float2*)f,
                                (float2*)g, cplx_n, scale);

@@ -40,7 +40,7 @@
 //
 // Pixels whose live window holds a non-finite sample (or one beyond the f16 range after standardising: |z| > 65504)
 // come out non-finite for every filter - 0 * inf - and are handed to valley.hip's kernel: this kernel stores norm = -1
-// (the norm proper is clipped at 0) and raises its tile's flag; the launcher then runs the direct kernel over the
+// (the norm proper is clipped at 0; -inf for a group of planes, whose best is kept unclipped: VrGroup) and raises its tile's flag; the launcher then runs the direct kernel over the
 // flagged tiles, which rewrites exactly the marked pixels.  Which pixels those are depends on their own window alone.
 //
 // Three kernels: valley_mfma_kernel over the live cells (any tables), valley_fold_kernel over PAIRS of opposite cells, which
@@ -91,6 +91,7 @@ struct VmArgs {
     int in_rows, in_row0, gny, nx;
     int out_row0, out_rows;
     float mean, stdev;
+    float floor, mark;          // VrGroup (common.hpp): the clip, and the mark of a pixel left to the direct kernel
 };
 
 // the maximum over the planes of an angle.  Plain fmaxf, which returns the other operand for a NaN like valley.hip's: no
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(kThreads, 2) void valley_mfma_kernel(VmArgs p) {
             unfinished = unfinished || !finite;
             const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
             if (h == 0)
-                p.norm[o] = finite ? fmaxf(b, 0.0f) : -1.0f;  // clip(min=0), topo.py:446; -1: left to the direct kernel
+                p.norm[o] = finite ? fmaxf(b, p.floor) : p.mark;  // clip(min=0), topo.py:446; mark: left to the direct kernel
             else
                 p.dir[o] = finite ? p.angles[bi] : 0.0f;
         }
@@ -313,6 +314,7 @@ struct VfArgs {
     int in_rows, in_row0, gny, nx;
     int out_row0, out_rows;
     float mean, stdev;
+    float floor, mark;
 };
 
 __host__ __device__ constexpr int fold_image_bytes(int w) {
@@ -461,7 +463,7 @@ __global__ __launch_bounds__(kThreads, 2) void valley_fold_kernel(VfArgs p) {
             unfinished = unfinished || !finite;
             const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
             if (h == 0)
-                p.norm[o] = finite ? fmaxf(b, 0.0f) : -1.0f;
+                p.norm[o] = finite ? fmaxf(b, p.floor) : p.mark;
             else
                 p.dir[o] = finite ? p.angles[bi] : 0.0f;
         }
@@ -504,6 +506,7 @@ struct VsArgs {
     int in_rows, in_row0, gny, nx;
     int out_row0, out_rows;
     float mean, stdev;
+    float floor, mark;
 };
 
 __host__ __device__ inline int stream_image_bytes(int w, int pitch, int ks) {
@@ -666,7 +669,7 @@ __global__ __launch_bounds__(kSThreads, 1) void valley_fold_stream_kernel(VsArgs
             unfinished = unfinished || !finite;
             const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
             if (h == 0)
-                p.norm[o] = finite ? fmaxf(b, 0.0f) : -1.0f;
+                p.norm[o] = finite ? fmaxf(b, p.floor) : p.mark;
             else
                 p.dir[o] = finite ? p.angles[bi] : 0.0f;
         }
@@ -713,14 +716,17 @@ int launch_ks(const VmArgs& a, dim3 grid) {
     return TOPO_AMD_OK;
 }
 
+// (the kernels hold NP planes per angle: a call with more planes must never reach a narrower instantiation)
 template <int KS>
 int launch_np(const VmArgs& a, dim3 grid, int n_planes) {
     switch (n_planes) {
         case 1: return launch_ks<KS, 1>(a, grid);
         case 2: return launch_ks<KS, 2>(a, grid);
         case 3: return launch_ks<KS, 3>(a, grid);
-        default: return launch_ks<KS, 4>(a, grid);
+        case 4: return launch_ks<KS, 4>(a, grid);
     }
+    TOPO_REQUIRE(false, "valley_ridge (matrix pipe): %d planes in one pass (1 to 4 are built)", n_planes);
+    return TOPO_AMD_EINVAL;
 }
 
 template <int KS, int NP>
@@ -738,8 +744,10 @@ int launch_fold_np(const VfArgs& a, dim3 grid, int n_planes) {
         case 1: return launch_fold_ks<KS, 1>(a, grid);
         case 2: return launch_fold_ks<KS, 2>(a, grid);
         case 3: return launch_fold_ks<KS, 3>(a, grid);
-        default: return launch_fold_ks<KS, 4>(a, grid);
+        case 4: return launch_fold_ks<KS, 4>(a, grid);
     }
+    TOPO_REQUIRE(false, "valley_ridge (matrix pipe, folded): %d planes in one pass (1 to 4 are built)", n_planes);
+    return TOPO_AMD_EINVAL;
 }
 
 template <int NP>
@@ -753,10 +761,10 @@ int launch_stream_np(const VsArgs& a, dim3 grid) {
 
 // The streamed folded form (launch_fold's classes and pairs): more than 15 K steps, or a window wider than the register-resident
 // kernels' LDS image.
-int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles, int n_planes, int W,
-                       double mean, double stdev, float* norm_out, float* dir_out, const int** flags_out, int* flag_cols, int* folded,
-                       int n_cls, const std::vector<int>& cls_of, const std::vector<int>& centre, const std::vector<int>* pair_of,
-                       const std::vector<int>* pair_cell) {
+int launch_fold_stream(const Block& b, const float* taps, const VrGroup& g, const int32_t* ksize, const float* angles, int n_angles,
+                       int n_planes, int W, double mean, double stdev, float* norm_out, float* dir_out, const int** flags_out,
+                       int* flag_cols, int* folded, int n_cls, const std::vector<int>& cls_of, const std::vector<int>& centre,
+                       const std::vector<int>* pair_of, const std::vector<int>* pair_cell) {
     int KS = 0;
     for (int c = 0; c < n_cls; ++c) KS = std::max(KS, ((int)pair_cell[c].size() + 15) / 16);
     KS = (KS + kSKC - 1) / kSKC * kSKC;
@@ -784,7 +792,7 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
         size_t at = 0;
         for (int ang = 0; ang < n_angles; ++ang) {
             first_tap[ang] = at;
-            at += (size_t)ksize[ang] * ksize[ang] * 4;
+            at += (size_t)ksize[ang] * ksize[ang] * g.stride;
         }
     }
     for (size_t pos = 0; pos < pos_angle.size(); ++pos) {
@@ -792,7 +800,7 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
         const int ks = ksize[ang], sh = W / 2 - ks / 2;
         const int tile = (int)pos / apt, hrow = ((int)pos % apt) / aph, slot = ((int)pos % apt) % aph;
         const int group = tile / kSTG, t_in = tile % kSTG;  // (groups run through both classes: a class's tiles fill whole groups)
-        const float* t = taps + first_tap[ang];
+        const float* t = taps + first_tap[ang] + g.p0;
         for (int ky = 0; ky < ks; ++ky)
             for (int kx = 0; kx < ks; ++kx) {
                 const int wy = ky + sh, wx = kx + sh, cell = wy * W + wx, other = (C - wy) * W + (C - wx);
@@ -800,7 +808,7 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
                 const int k = pair_of[c][cell];
                 if (k < 0) continue;
                 for (int q = 0; q < n_planes; ++q) {
-                    float v = t[((size_t)ky * ks + kx) * 4 + q];
+                    float v = t[((size_t)ky * ks + kx) * g.stride + q];
                     if (v == 0.0f) continue;
                     if (cell == other) v *= 0.5f;
                     const uint16_t hi = f16_bits(v);
@@ -822,7 +830,8 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
         unsigned short* k16 = reinterpret_cast<unsigned short*>(ints.data());
         for (int c = 0; c < n_cls; ++c)
             for (int k = 0; k < KS * 16; ++k) {
-                const int cell = pair_cell[c][k < (int)pair_cell[c].size() ? k : 0];
+                // behind the last live pair: the first one again, against zero taps (cell 0 for a class without taps)
+                const int cell = k < (int)pair_cell[c].size() ? pair_cell[c][k] : pair_cell[c].empty() ? 0 : pair_cell[c][0];
                 k16[(size_t)c * KS * 16 + k] = (unsigned short)((cell / W) * pitch + cell % W);
             }
     }
@@ -859,6 +868,8 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
     a.out_rows = b.out_rows;
     a.mean = (float)mean;
     a.stdev = (float)stdev;
+    a.floor = g.floor;
+    a.mark = g.mark;
     *flags_out = (const int*)d_flags;
     *flag_cols = (int)grid.x;
     *folded = 2;
@@ -866,31 +877,36 @@ int launch_fold_stream(const Block& b, const float* taps, const int32_t* ksize, 
         case 1: return launch_stream_np<1>(a, grid);
         case 2: return launch_stream_np<2>(a, grid);
         case 3: return launch_stream_np<3>(a, grid);
-        default: return launch_stream_np<4>(a, grid);
+        case 4: return launch_stream_np<4>(a, grid);
     }
+    TOPO_REQUIRE(false, "valley_ridge (matrix pipe, streamed): %d planes in one pass (1 to 4 are built)", n_planes);
+    return TOPO_AMD_EINVAL;
 }
 
 // The folded form, if the tables allow it: every kernel bit for bit point-symmetric, at most two canvas centres in the common
 // window, at most 15 K steps of live pairs (kernels of up to 17 px).  *folded = 0: not such a case, nothing launched.
-int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles, int n_planes, int W,
-                double mean, double stdev, float* norm_out, float* dir_out, const int** flags_out, int* flag_cols, int* folded) {
+int launch_fold(const Block& b, const float* taps, const VrGroup& g, const int32_t* ksize, const float* angles, int n_angles,
+                int n_planes, int W, double mean, double stdev, float* norm_out, float* dir_out, const int** flags_out, int* flag_cols,
+                int* folded) {
     *folded = 0;
-    // symmetry, and the class of every angle: the window cell opposite (wy, wx) is (C - wy, C - wx), C = ks - 1 + 2 (W / 2 - ks / 2)
+    const int S = g.stride;
+    // symmetry (of every plane of the call: all groups take the same form), and the class of every angle: the window cell
+    // opposite (wy, wx) is (C - wy, C - wx), C = ks - 1 + 2 (W / 2 - ks / 2)
     std::vector<int> cls_of(n_angles), centre;
     const float* src = taps;
     for (int ang = 0; ang < n_angles; ++ang) {
         const int ks = ksize[ang];
         for (int ky = 0; ky < ks; ++ky)
             for (int kx = 0; kx < ks; ++kx)
-                for (int q = 0; q < n_planes; ++q)
-                    if (src[((size_t)ky * ks + kx) * 4 + q] != src[((size_t)(ks - 1 - ky) * ks + (ks - 1 - kx)) * 4 + q]) return TOPO_AMD_OK;
+                for (int q = 0; q < g.n_live; ++q)
+                    if (src[((size_t)ky * ks + kx) * S + q] != src[((size_t)(ks - 1 - ky) * ks + (ks - 1 - kx)) * S + q]) return TOPO_AMD_OK;
         const int C = ks - 1 + 2 * (W / 2 - ks / 2);
         size_t k = 0;
         while (k < centre.size() && centre[k] != C) ++k;
         if (k == centre.size()) centre.push_back(C);
         if (centre.size() > 2) return TOPO_AMD_OK;
         cls_of[ang] = (int)k;
-        src += (size_t)ks * ks * 4;
+        src += (size_t)ks * ks * S;
     }
     const int n_cls = (int)centre.size();
     // the live pairs of each class (a pair by its first cell in row-major order), and each angle's taps on its class's pairs
@@ -903,14 +919,14 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
         for (int ky = 0; ky < ks; ++ky)
             for (int kx = 0; kx < ks; ++kx) {
                 bool any = false;
-                for (int q = 0; q < n_planes; ++q) any = any || src[((size_t)ky * ks + kx) * 4 + q] != 0.0f;
+                for (int q = 0; q < g.n_live; ++q) any = any || src[((size_t)ky * ks + kx) * S + q] != 0.0f;
                 if (!any) continue;
                 const int wy = ky + sh, wx = kx + sh, oy = C - wy, ox = C - wx;
                 if (oy < 0 || oy >= W || ox < 0 || ox >= W) return TOPO_AMD_OK;  // (cannot happen: the partner is a cell of the same canvas)
                 const int cell = std::min(wy * W + wx, oy * W + ox);
                 if (pair_of[c][cell] < 0) pair_of[c][cell] = -2;  // live; numbered below in row-major order
             }
-        src += (size_t)ks * ks * 4;
+        src += (size_t)ks * ks * S;
     }
     int KS = 0;
     for (int c = 0; c < n_cls; ++c) {
@@ -923,8 +939,8 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
     }
     if (KS < 1) return TOPO_AMD_OK;
     if (KS > kMaxSteps || W > kValleyMfmaMaxKernel)
-        return launch_fold_stream(b, taps, ksize, angles, n_angles, n_planes, W, mean, stdev, norm_out, dir_out, flags_out, flag_cols,
-                                  folded, n_cls, cls_of, centre, pair_of, pair_cell);
+        return launch_fold_stream(b, taps, g, ksize, angles, n_angles, n_planes, W, mean, stdev, norm_out, dir_out, flags_out,
+                                  flag_cols, folded, n_cls, cls_of, centre, pair_of, pair_cell);
     const int aph = 16 / n_planes, apt = 2 * aph, gt = group_tiles(KS);
     // the stream: the tiles of class 0 (its angles in rising order, the last group filled with copies of its last angle), then class 1
     std::vector<int> pos_angle;
@@ -946,14 +962,14 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
         size_t at = 0;
         for (int ang = 0; ang < n_angles; ++ang) {
             first_tap[ang] = at;
-            at += (size_t)ksize[ang] * ksize[ang] * 4;
+            at += (size_t)ksize[ang] * ksize[ang] * S;
         }
     }
     for (size_t pos = 0; pos < pos_angle.size(); ++pos) {
         const int ang = pos_angle[pos], c = cls_of[ang], C = centre[c];
         const int ks = ksize[ang], sh = W / 2 - ks / 2;
         const int tile = (int)pos / apt, hrow = ((int)pos % apt) / aph, slot = ((int)pos % apt) % aph;
-        const float* t = taps + first_tap[ang];
+        const float* t = taps + first_tap[ang] + g.p0;
         for (int ky = 0; ky < ks; ++ky)
             for (int kx = 0; kx < ks; ++kx) {
                 const int wy = ky + sh, wx = kx + sh, cell = wy * W + wx, other = (C - wy) * W + (C - wx);
@@ -961,7 +977,7 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
                 const int k = pair_of[c][cell];
                 if (k < 0) continue;
                 for (int q = 0; q < n_planes; ++q) {
-                    float v = t[((size_t)ky * ks + kx) * 4 + q];
+                    float v = t[((size_t)ky * ks + kx) * S + q];
                     if (v == 0.0f) continue;
                     if (cell == other) v *= 0.5f;  // the centre cell is its own partner: z + z against half the tap (exact)
                     const uint16_t hi = f16_bits(v);
@@ -978,7 +994,8 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
     std::vector<int> koff((size_t)2 * KS * 16 * 2, 0);
     for (int c = 0; c < n_cls; ++c)
         for (int k = 0; k < KS * 16; ++k) {
-            const int cell = pair_cell[c][k < (int)pair_cell[c].size() ? k : 0];  // behind the last live pair: the first one, zero taps
+            // behind the last live pair: the first one again, against zero taps (cell 0 for a class without taps)
+            const int cell = k < (int)pair_cell[c].size() ? pair_cell[c][k] : pair_cell[c].empty() ? 0 : pair_cell[c][0];
             const int wy = cell / W, wx = cell % W;
             koff[((size_t)c * KS * 16 + k) * 2] = wy * kPitch + wx;
             koff[((size_t)c * KS * 16 + k) * 2 + 1] = (centre[c] - wy) * kPitch + (centre[c] - wx);
@@ -1017,6 +1034,8 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
     a.out_rows = b.out_rows;
     a.mean = (float)mean;
     a.stdev = (float)stdev;
+    a.floor = g.floor;
+    a.mark = g.mark;
     *flags_out = (const int*)d_flags;
     *flag_cols = (int)grid.x;
     *folded = 1;
@@ -1034,18 +1053,20 @@ int launch_fold(const Block& b, const float* taps, const int32_t* ksize, const f
 // The matrix-pipe evaluation over the block.  *done = 0: not a case for it (no live cell, or more than 240), nothing
 // launched; 1: the kernel over the live cells; 2: the folded form (point-symmetric tables).  Otherwise *flags_out / *flag_cols describe the tiles (kValleyMfmaTileRows rows x 64 columns, anchored at
 // out_row0) in which it left pixels marked norm = -1 for the direct kernel.
-int launch_valley_ridge_mfma(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles,
-                             int n_planes, int kmax, double mean, double stdev, float* norm_out, float* dir_out,
+int launch_valley_ridge_mfma(const Block& b, const float* taps, const VrGroup& g, const int32_t* ksize, const float* angles,
+                             int n_angles, int n_planes, int kmax, double mean, double stdev, float* norm_out, float* dir_out,
                              const int** flags_out, int* flag_cols, int* done) {
     *done = 0;
     TOPO_REQUIRE(kmax >= 1 && kmax <= kValleyStreamMaxKernel, "valley_ridge (matrix pipe): kernel side %d", kmax);
+    TOPO_REQUIRE(n_planes >= 1 && n_planes <= 4 && g.p0 >= 0 && g.p0 + n_planes <= g.stride && g.n_live <= g.stride,
+                 "valley_ridge (matrix pipe): planes %d .. %d of taps of %d floats", g.p0, g.p0 + n_planes - 1, g.stride);
     const int W = kmax;  // the window = the largest canvas (a smaller one sits inside it: it starts ks / 2 before the pixel)
     {
         const char* e = std::getenv("TOPO_AMD_VALLEY_FOLD");  // 0: never the folded form (read at every launch; tests)
         if (!(e && *e == '0')) {
             int folded = 0;
-            TOPO_TRY(launch_fold(b, taps, ksize, angles, n_angles, n_planes, W, mean, stdev, norm_out, dir_out, flags_out, flag_cols,
-                                 &folded));
+            TOPO_TRY(launch_fold(b, taps, g, ksize, angles, n_angles, n_planes, W, mean, stdev, norm_out, dir_out, flags_out,
+                                 flag_cols, &folded));
             if (folded) {
                 *done = 1 + folded;  // 2: the operands in registers, 3: streamed
                 return TOPO_AMD_OK;
@@ -1061,15 +1082,15 @@ int launch_valley_ridge_mfma(const Block& b, const float* taps, const int32_t* k
         const int ks = ksize[ang];
         const int shift = W / 2 - ks / 2;
         for (int ky = 0; ky < ks; ++ky)
-            for (int kx = 0; kx < ks; ++kx)
-                for (int q = 0; q < n_planes; ++q) {
-                    const float t = src[((size_t)ky * ks + kx) * 4 + q];
-                    if (t == 0.0f) continue;
-                    const size_t cell = (size_t)(ky + shift) * W + kx + shift;
-                    canvas[((size_t)ang * n_planes + q) * W * W + cell] = t;
-                    live_cell[cell] = 1;
-                }
-        src += (size_t)ks * ks * 4;
+            for (int kx = 0; kx < ks; ++kx) {
+                const float* tap = src + ((size_t)ky * ks + kx) * g.stride;
+                const size_t cell = (size_t)(ky + shift) * W + kx + shift;
+                for (int q = 0; q < g.n_live; ++q)  // the window: the cells with a tap in any plane of the call
+                    if (tap[q] != 0.0f) live_cell[cell] = 1;
+                for (int q = 0; q < n_planes; ++q)
+                    if (tap[g.p0 + q] != 0.0f) canvas[((size_t)ang * n_planes + q) * W * W + cell] = tap[g.p0 + q];
+            }
+        src += (size_t)ks * ks * g.stride;
     }
     std::vector<int> live;
     for (int c = 0; c < W * W; ++c)
@@ -1134,6 +1155,8 @@ int launch_valley_ridge_mfma(const Block& b, const float* taps, const int32_t* k
     a.out_rows = b.out_rows;
     a.mean = (float)mean;
     a.stdev = (float)stdev;
+    a.floor = g.floor;
+    a.mark = g.mark;
     *flags_out = (const int*)d_flags;
     *flag_cols = (int)grid.x;
     *done = 1;

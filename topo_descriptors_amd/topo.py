@@ -376,6 +376,9 @@ def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_st
 
 
 # ---- valley / ridge index ---------------------------------------------------------------------
+VALLEY_MAX_PLANES = 16  # flat fractions per call (TOPO_AMD_VALLEY_MAX_PLANES, include/topo_amd.h)
+
+
 def _valley_kernels(size, flat_list):
     """One normalised V / U profile per flat fraction (reference topo.py:456-492): distance to the
     centre row, repeated along the columns; a fraction ``f`` flattens the band of half-width
@@ -424,17 +427,19 @@ def _valley_ridge_tables(kernels, angles):
     The DEM is broadcast to one identical plane per kernel plane, so along that axis the "same"
     convolution just adds the kernel planes that overlap: output plane ``i`` of ``L`` sees the sum of
     ``K[b]`` with ``0 <= i - b + (L - 1) // 2 < L`` (three planes: K0+K1, K0+K1+K2, K1+K2).  The
-    sums are flipped in both axes (a convolution becomes a correlation) and interleaved as four
-    floats per tap.  Returns (taps float32, ksize int32, angles float32)."""
+    sums are flipped in both axes (a convolution becomes a correlation) and interleaved as
+    ``4 * ceil(n / 4)`` floats per tap: group ``g`` holds planes ``4g .. 4g+3``, unused slots are 0
+    (four floats for up to four planes).  Returns (taps float32, ksize int32, angles float32)."""
     n = kernels.shape[0]
-    if not 1 <= n <= 4:
-        raise ValueError(f"valley_ridge: {n} flat fractions; 1 to 4 are supported")
+    if not 1 <= n <= VALLEY_MAX_PLANES:
+        raise ValueError(f"valley_ridge: {n} flat fractions; 1 to {VALLEY_MAX_PLANES} are supported")
     centre = (n - 1) // 2
+    width = 4 * ((n + 3) // 4)
 
     def one_angle(angle):
         turned = _rotate_kernels(kernels, angle).astype(np.float64)
         side = turned.shape[1]
-        block = np.zeros((side, side, 4), dtype=np.float32)
+        block = np.zeros((side, side, width), dtype=np.float32)
         for i in range(n):
             total = sum(turned[b] for b in range(n) if 0 <= i - b + centre < n)
             block[:, :, i] = total[::-1, ::-1]
@@ -449,7 +454,7 @@ def _valley_ridge_tables(kernels, angles):
             taps = list(pool.map(one_angle, angles))
     else:
         taps = [one_angle(angle) for angle in angles]
-    ksize = [int(round((t.size // 4) ** 0.5)) for t in taps]
+    ksize = [int(round((t.size // width) ** 0.5)) for t in taps]
     return (np.ascontiguousarray(np.concatenate(taps), dtype=np.float32), np.asarray(ksize, dtype=np.int32),
             np.ascontiguousarray(angles, dtype=np.float32))
 
