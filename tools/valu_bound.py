@@ -13,14 +13,14 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r07_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r09_tpi67_wide_valu_count.json
 
 wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
-row loop per VALID output column: offline, before any GPU time.  A chain wave's two rows of a phase are unrolled into
-the phase loop (three ds_read_b64 per prefix row), and the first row is the stretch from its s_setprio 3 to the second
-row's s_setprio 1 (its own reads after the two it leads with, the chain, the finalisation and the stores, then the
-second row's two leading reads).  Vector adds whose result is a ds_read address are counted as their own class.
+row loop per VALID output column: offline, before any GPU time.  A chain wave sums its two rows of a phase in one sweep
+(55 distinct prefix rows of three ds_read_b64 for the pair), so the count is that of the chain waves' phase loop - the
+sweep, the finalisation and the stores of both rows, the barrier - and an output row is half of it.  Vector adds whose
+result is a ds_read address are counted as their own class.
 
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
@@ -122,27 +122,33 @@ def wide():
                         "--cuda-device-only", os.path.join(REPO, "tools", "ubench", "tpi_lab.hip"), "-o", lab],
                        check=True, stderr=subprocess.DEVNULL)
         txt_m = open(lab).read()
-    # the phase loop with both rows of a chain wave (2 x 42 prefix rows, three ds_read_b64 each, the float64 finalisation);
-    # one row: from the first row's s_setprio 3 to the second row's s_setprio 1
-    ph = loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 2 * 3 * 42 and any("f64" in x for x in o))
+    # the chain waves' phase loop: ONE sweep over the wave's row pair (55 distinct prefix rows of the pair's 84, three
+    # ds_read_b64 each), the float64 finalisation and the stores of both rows, the barrier; an output row is half of it
+    ph = loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 3 * 42 and any("f64" in x for x in o))
     mn = [x.split()[0] for x in ph]
-    a = next(i for i, x in enumerate(ph) if x == "s_setprio 3")
-    b = next(i for i, x in enumerate(ph) if i > a and x == "s_setprio 1")
-    row = ph[a:b]
-    o = [x.split()[0] for x in row]
-    assert mn.count("ds_read_b64") == 2 * o.count("ds_read_b64") == 2 * 3 * 42, "one row: 42 prefix rows of three reads"
+    assert mn.count("ds_read_b64") == 3 * 55, "a row pair: 55 prefix rows of three reads"
+    assert mn.count("s_setprio") in (0, 4), "no priority ladder, or the sweep's 3, 2, 1, 0 (WIDE_PRIO)"
+    row = ph
+    o = mn
     n_addr = address_adds(row)
     om = loop_ops(txt_m, KERNEL, lambda o: 42 <= sum(x == "ds_read_b128" for x in o) <= 46 and any("f64" in x for x in o))
     valu, kinds, ns = price(o)
     valu_m, kinds_m, ns_m = price(om)
     kinds["plain"] -= n_addr  # (plain adds: priced as before)
     kinds["ds_read_address"] = n_addr
+    pair = {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b64": o.count("ds_read_b64"), "s_nop": o.count("s_nop"),
+            "salu": sum(1 for x in o if x.startswith("s_")), "ns": round(ns, 1)}
+    # per output row: half the pair
+    valu = valu[:len(valu) // 2]
+    kinds = Counter({k: v / 2 for k, v in kinds.items()})
+    ns /= 2
     cols, cols_m = 312, TILE_W
     print(json.dumps({
-        "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns) of the phase loop",
-        "row_loop_instructions": {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128"),
-                                  "ds_read_b64": o.count("ds_read_b64"), "v_mov_b32_dpp": o.count("v_mov_b32_dpp"),
-                                  "s_nop": o.count("s_nop"), "salu": sum(1 for x in o if x.startswith("s_"))},
+        "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns): half the row pair of the phase loop",
+        "row_pair_instructions": pair,
+        "row_loop_instructions": {"valu": pair["valu"] / 2, "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128") / 2,
+                                  "ds_read_b64": o.count("ds_read_b64") / 2, "v_mov_b32_dpp": o.count("v_mov_b32_dpp") / 2,
+                                  "s_nop": o.count("s_nop") / 2, "salu": sum(1 for x in o if x.startswith("s_")) / 2},
         "ns_per_wave_row": round(ns, 1),
         "valid_columns_per_wave_row": cols,
         "marching_kernel": {"kernel": "tpi_march_kernel<67, 60, 12, true, true, true>", "valu": len(valu_m), "by_kind": dict(kinds_m),

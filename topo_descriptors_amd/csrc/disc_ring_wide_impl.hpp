@@ -10,7 +10,9 @@
 //     +0, +8 and +16 from byte 24 l (dwords 6 l, 6 l + 1 of the 32 lanes of a group are distinct mod 64: conflict-free);
 //   * the ring holds R = SIZE + 32 rows plus GR = 6 guard rows behind them, copies of slots 0 .. GR - 1 (WideCfg), so
 //     that one VGPR address at slot (s0 + k) mod R reaches the rows k .. k + GR of the window by immediate offsets: nine
-//     addresses a row (WBase) instead of one per read;
+//     addresses a row pair (WPair) instead of one per read;
+//   * a chain wave sums its two rows of a phase in ONE sweep (wide_pair_sum): the pair needs 55 distinct prefix rows at
+//     67 px where two single rows read 84, and each is read once;
 //   * the staging runs on waves of its own (std_ring_spec_kernel's structure):
 //     waves 0-2 convert, classify and write batch ph + 1 (16 rows, two columns per lane, 8-byte loads) and issue the
 //     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase;
@@ -110,186 +112,265 @@ constexpr bool tpi_wide_ring_fits(int size) {
     return size >= 5 && size % 2 == 1 && (size_t)(size + 32 + 6) * 384 * 4 + 64 <= 160 * 1024 && 64 - 2 * ((size / 2 + 5) / 6) >= 16;
 }
 
-// The VGPR addresses of a row's prefix-row reads.  The chain reads run r at Q indices top = run_hi + 1 + M and
-// bot = run_lo + M, in the order WGeo::S.order.  A base at Q index kb is the one VGPR 24 lane + ((s0 + kb) mod R) PB; a read
-// at k with kb <= k <= kb + GR is that base plus the immediate (k - kb) PB (+0, +8, +16): it lands in slot
-// (s0 + kb) mod R + k - kb <= R - 1 + GR, a guard row where the ring wraps.  The bases cover the read indices greedily from
-// the smallest, and each is formed at the first fetch that needs it (so it lives only over its stretch of the sweep).
+// The prefix-row reads of a chain wave's row pair, rows A and B = A + 1 of a phase, in Q indices of row A's window
+// (0 .. 2 M + 2; row B's index k is row A's k + 1).  Run r of row A reads top = run_hi + 1 + M and bot = run_lo + M, of row
+// B the rows one below: the top row of B at height h is the top row of A at height h + 1 and the bottom row of B at
+// height h the bottom row of A at height h - 1, so wherever the disc's run heights are consecutive the pair needs each
+// of those rows once.  A distinct row is loaded by the first fetch (index into WGeo::S.order) that needs it and stays in
+// registers until the last that does; use[i][w][e] names the row that serves fetch i, row w of the pair, top (e = 0) or
+// bottom (e = 1) - the Q index itself.
+// The VGPR addresses: a base at Q index kb is the one VGPR 24 lane + ((s0 + kb) mod R) PB; a read at k with
+// kb <= k <= kb + GR is that base plus the immediate (k - kb) PB (+0, +8, +16): it lands in slot
+// (s0 + kb) mod R + k - kb <= R - 1 + GR, a guard row where the ring wraps.  The bases cover the distinct rows greedily from
+// the smallest, and each is formed at the first fetch that loads through it (so it lives only over its stretch of the sweep).
 template <int SIZE, int GR>
-struct WBase {
+struct WPair {
     using G = WGeo<SIZE>;
     static constexpr int NR = G::NR;
+    static constexpr int NK = 2 * G::M + 3;  // Q indices of the pair
     struct Tab {
-        int nb;           // bases
-        int kb[2 * SIZE]; // Q index of base b
-        int first[2 * SIZE];  // fetch (index into S.order) that forms base b
-        int top_b[SIZE], bot_b[SIZE];  // per fetch i: base of the top / bottom read
-        int top_k[SIZE], bot_k[SIZE];  // per fetch i: Q index of the top / bottom read
+        int rows;              // distinct prefix rows of the pair
+        int nb;                // bases
+        int kb[NK];            // Q index of base b
+        int first[NK];         // fetch that forms base b
+        int base[NK];          // per Q index: the base its read goes through
+        int use[SIZE][2][2];   // per fetch, row of the pair, top / bottom: the Q index that serves it
+        int nload[SIZE];       // per fetch: rows it loads
+        int load[SIZE][4];     // ... and their Q indices
     };
     static constexpr Tab make() {
         Tab t{};
-        bool need[2 * SIZE + 2] = {};
+        bool need[NK] = {};
         for (int i = 0; i < NR; ++i) {
             const int r = G::S.order[i];
-            t.top_k[i] = G::T.run_hi[r] + 1 + G::M;
-            t.bot_k[i] = G::T.run_lo[r] + G::M;
-            need[t.top_k[i]] = need[t.bot_k[i]] = true;
+            for (int w = 0; w < 2; ++w) {
+                t.use[i][w][0] = G::T.run_hi[r] + 1 + G::M + w;
+                t.use[i][w][1] = G::T.run_lo[r] + G::M + w;
+            }
+            for (int w = 0; w < 2; ++w)
+                for (int e = 0; e < 2; ++e) {
+                    const int k = t.use[i][w][e];
+                    if (!need[k]) t.load[i][t.nload[i]++] = k;
+                    need[k] = true;
+                }
         }
-        t.nb = 0;
-        for (int k = 0; k <= 2 * G::M + 1; ++k)
-            if (need[k] && (t.nb == 0 || k > t.kb[t.nb - 1] + GR)) t.kb[t.nb++] = k;
+        for (int k = 0; k < NK; ++k) {
+            if (!need[k]) continue;
+            ++t.rows;
+            if (t.nb == 0 || k > t.kb[t.nb - 1] + GR) t.kb[t.nb++] = k;
+            t.base[k] = t.nb - 1;
+        }
         for (int b = 0; b < t.nb; ++b) t.first[b] = NR;
-        auto base_of = [&](int k) {
-            int b = 0;
-            while (b + 1 < t.nb && t.kb[b + 1] <= k) ++b;
-            return b;
-        };
-        for (int i = 0; i < NR; ++i) {
-            t.top_b[i] = base_of(t.top_k[i]);
-            t.bot_b[i] = base_of(t.bot_k[i]);
-            if (i < t.first[t.top_b[i]]) t.first[t.top_b[i]] = i;
-            if (i < t.first[t.bot_b[i]]) t.first[t.bot_b[i]] = i;
-        }
+        for (int i = NR - 1; i >= 0; --i)
+            for (int n = 0; n < t.nload[i]; ++n) t.first[t.base[t.load[i][n]]] = i;
         return t;
     }
     static constexpr Tab T = make();
     static constexpr bool check() {
-        for (int i = 0; i < NR; ++i)
-            if (T.top_k[i] - T.kb[T.top_b[i]] > GR || T.top_k[i] < T.kb[T.top_b[i]] || T.bot_k[i] - T.kb[T.bot_b[i]] > GR ||
-                T.bot_k[i] < T.kb[T.bot_b[i]])
-                return false;
+        bool loaded[NK] = {};
+        for (int i = 0; i < NR; ++i) {
+            for (int n = 0; n < T.nload[i]; ++n) {
+                const int k = T.load[i][n], b = T.base[k];
+                if (k < T.kb[b] || k - T.kb[b] > GR || T.first[b] > i || loaded[k]) return false;
+                loaded[k] = true;
+            }
+            for (int w = 0; w < 2; ++w)
+                for (int e = 0; e < 2; ++e)
+                    if (!loaded[T.use[i][w][e]]) return false;
+        }
         return true;
     }
-    static_assert(check(), "every read within GR rows of its base");
+    // the rows a pair would read without sharing (four a run), and what the run heights of the disc leave of them
+    static constexpr int kUnshared = 4 * NR;
+    static_assert(check(), "every row loaded once, before its uses, within GR rows of a base formed by then");
+    static_assert(T.rows < kUnshared, "the pair shares no prefix row");
+    static_assert(SIZE != 67 || T.rows == 55, "67 px: 55 distinct prefix rows a pair (84 unshared)");
+};
+
+// (a loop whose index is a constant expression in its body: if constexpr on the disc's tables)
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void wide_static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        wide_static_for<N, I + 1>(f);
+    }
+}
+
+// The joint sweep's order of sums: the runs in the order WGeo::S.order, the lane's columns s = 0 .. NCW - 1 of each.
+// firstR[D][t] (firstL) is j NCW + s of the first difference that goes into step D of the right (left) chain for output
+// t - the one that starts the sum - or -1 where the lane's own columns give that step nothing.
+template <int SIZE>
+struct WSweep {
+    using G = WGeo<SIZE>;
+    struct Tab {
+        int firstR[G::DL + 1][NCW], firstL[G::DL + 1][NCW];
+    };
+    static constexpr Tab make() {
+        Tab t{};
+        for (int D = 0; D <= G::DL; ++D)
+            for (int o = 0; o < NCW; ++o) t.firstR[D][o] = t.firstL[D][o] = -1;
+        for (int j = G::NR - 1; j >= 0; --j)
+            for (int s = NCW - 1; s >= 0; --s)
+                for (int D = 0; D <= G::DL; ++D)
+                    for (int o = 0; o < NCW; ++o) {
+                        const int dr = NCW * D + s - o, dl = -NCW * D + s - o;
+                        if (dr >= 0 && dr <= G::M && G::T.run_of[dr - G::T.off_min] == G::S.order[j]) t.firstR[D][o] = j * NCW + s;
+                        if (dl < 0 && dl >= -G::M && G::T.run_of[dl - G::T.off_min] == G::S.order[j]) t.firstL[D][o] = j * NCW + s;
+                    }
+        return t;
+    }
+    static constexpr Tab T = make();
+    // issue priority over the steps DL ... 0: 3 at the first, 0 at the last
+    static constexpr int prio_of(int D) { return 3 - (G::DL - D) * 4 / (G::DL + 1); }
 };
 
 #ifndef WIDE_LEAD
 #define WIDE_LEAD 2
 #endif
+// (lab switch: 1 runs the sweep under the issue-priority ladder of wide_pair_sum; measured slower than without, see there)
 #ifndef WIDE_PRIO
-#define WIDE_PRIO 1
+#define WIDE_PRIO 0
 #endif
 
 typedef uint32_t u32x2w __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const char lds_char;
 typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 
-// Disc sums of one output row (ring_disc_sum with 6 columns per lane): s0 is the ring slot of the row's Q index 0,
-// acc[t] the sum for the lane's column NCW lane + t (valid for DL <= lane < 64 - DL), ctr[t] that pixel's own value.
-// FIRST (WIDE_PRIO): the wave's first row of the phase - its issue priority goes 3 -> 2 over that row and 1 -> 0 over the
-// second (CHAIN_PRIO, disc_wave_impl.hpp), so that the two chain waves of a SIMD advance together.  A template argument,
-// so that no branch splits the chain: a DPP move and the add it feeds fold into one DPP add only within a basic block.
-template <int SIZE, int R, int GR, int LEAD, bool FIRST>
-__device__ __forceinline__ void wide_disc_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[NCW], uint32_t (&ctr)[NCW]) {
+// Disc sums of the two output rows of a chain wave in ONE sweep (ring_disc_sum with 6 columns per lane, two rows): s0 is
+// the ring slot of Q index 0 of row A's window, acc[w][t] the sum of row w for the lane's column NCW lane + t (valid for
+// DL <= lane < 64 - DL), ctr[w][t] that pixel's own value.  The runs go in the order WGeo::S.order; fetch i loads the
+// prefix rows of the pair that no earlier fetch has loaded (WPair), and both rows' differences of a run are formed from
+// the loaded rows, the shared ones among them.
+// PRIO (WIDE_PRIO, off): the wave's issue priority goes 3 -> 2 -> 1 -> 0 over the sweep's steps (CHAIN_PRIO,
+// disc_wave_impl.hpp), the counterpart of the 3 -> 2, 1 -> 0 pair that made the two chain waves of a SIMD advance together
+// when each summed its two rows one after the other.  With ONE sweep per wave and phase it loses: a bench step took
+// 4.12 - 4.13 ms with the ladder where the two-sweep kernel took 3.66 - 3.69 ms, and without it 3.38 ms against 3.50 ms
+//  - the chain waves then outrank the staging waves for most of a phase, and the barrier waits for
+// those.  A compile-time choice, and no branch in the sweep either
+// way: a DPP move and the add it feeds fold into one DPP add only within a basic block.
+template <int SIZE, int R, int GR, int LEAD, bool PRIO>
+__device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[2][NCW], uint32_t (&ctr)[2][NCW]) {
     using G = WGeo<SIZE>;
-    using BT = WBase<SIZE, GR>;
+    using PT = WPair<SIZE, GR>;
+    using SW_ = WSweep<SIZE>;
     constexpr int NR = G::NR;
     constexpr int DL = G::DL;
     constexpr int M = G::M;
     constexpr uint32_t PB = (uint32_t)G::W * 4;  // bytes per ring row
     constexpr uint32_t RB = (uint32_t)R * PB;
-    u32x2w top[NR][3], bot[NR][3];
-    uint32_t cv[NR][NCW];
-    uint32_t aR[NCW], aL[NCW];
-    uint32_t vb[BT::T.nb];
+    u32x2w row[PT::NK][3];
+    // pR[w][D][t], pL[w][D][t]: what the lane's own columns give step D of row w's right / left chain for output t, summed
+    // run by run as the differences are formed (a difference goes into every step that takes it at once and is not
+    // kept: one sweep holds the open steps' sums of two rows, not two rows' differences of the runs in flight)
+    uint32_t pR[2][DL + 1][NCW], pL[2][DL + 1][NCW];
+    uint32_t aR[2][NCW], aL[2][NCW];
+    uint32_t vb[PT::T.nb];
     lds_char* q = (lds_char*)ring;
     const uint32_t b0 = (uint32_t)s0 * PB, lb = (uint32_t)lane * (NCW * 4);
-    auto fetch = [&](int i) {
-        const int r = G::S.order[i];
+    auto fetch = [&](auto I) {
+        constexpr int i = decltype(I)::value;
 #pragma unroll
-        for (int b = 0; b < BT::T.nb; ++b)
-            if (BT::T.first[b] == i) {
-                const uint32_t d = b0 + (uint32_t)BT::T.kb[b] * PB;
+        for (int b = 0; b < PT::T.nb; ++b)
+            if (PT::T.first[b] == i) {
+                const uint32_t d = b0 + (uint32_t)PT::T.kb[b] * PB;
                 vb[b] = lb + min(d, d - RB);  // the scalar wrap, then one vector add
                 asm("" : "+v"(vb[b]));        // (opaque: every read of the base keeps it and takes an immediate offset)
             }
-        lds_char* pt = q + vb[BT::T.top_b[i]] + (uint32_t)(BT::T.top_k[i] - BT::T.kb[BT::T.top_b[i]]) * PB;
-        lds_char* pb = q + vb[BT::T.bot_b[i]] + (uint32_t)(BT::T.bot_k[i] - BT::T.kb[BT::T.bot_b[i]]) * PB;
-        // (volatile: three ds_read_b64, not merged into ds_read2_b64, which banks 32 wide and moves half as many bytes a cycle)
 #pragma unroll
-        for (int h = 0; h < 3; ++h) top[r][h] = *(lds_u32x2w*)(pt + 8 * h);
+        for (int n = 0; n < PT::T.nload[i]; ++n) {
+            const int k = PT::T.load[i][n];
+            lds_char* pk = q + vb[PT::T.base[k]] + (uint32_t)(k - PT::T.kb[PT::T.base[k]]) * PB;
+            // (volatile: three ds_read_b64, not merged into ds_read2_b64, which banks 32 wide and moves half as many bytes a cycle)
 #pragma unroll
-        for (int h = 0; h < 3; ++h) bot[r][h] = *(lds_u32x2w*)(pb + 8 * h);
+            for (int h = 0; h < 3; ++h) row[k][h] = *(lds_u32x2w*)(pk + 8 * h);
+        }
     };
-#pragma unroll
-    for (int i = 0; i < LEAD && i < NR; ++i) fetch(i);
-#if WIDE_PRIO
-    if (FIRST) CHAIN_SETPRIO(3);
-    else CHAIN_SETPRIO(1);
-#endif
-    static_assert(DL >= 1, "the last step (D = 0) closes both chains");
-#pragma unroll
-    for (int D = DL; D >= 0; --D) {
-#if WIDE_PRIO
-        if (D == DL / 2) {
-            if (FIRST) CHAIN_SETPRIO(2);
-            else CHAIN_SETPRIO(0);
-        }
-#endif
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            if (G::S.first_step[G::S.order[j]] == D) {
-                const int r = G::S.order[j];
-                if (j + LEAD < NR) fetch(j + LEAD);
-                RING_SB();
-#pragma unroll
-                for (int s = 0; s < NCW; ++s) cv[r][s] = top[r][s / 2][s % 2] - bot[r][s / 2][s % 2];
-                RING_SB();
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NCW; ++t) {
+    // step D of the chains of both rows: the lane's own part, then the hop
+    auto close = [&](auto DD) {
+        constexpr int D = decltype(DD)::value;
+        wide_static_for<NCW * 2>([&](auto TW) {
+            constexpr int t = decltype(TW)::value / 2, w = decltype(TW)::value % 2;
+            constexpr bool anyr = SW_::T.firstR[D][t] >= 0, anyl = SW_::T.firstL[D][t] >= 0;
             uint32_t pr = 0, pl = 0;
-            bool anyr = false, anyl = false;
-#pragma unroll
-            for (int s = 0; s < NCW; ++s) {
-                const int dr = NCW * D + s - t;
-                const int dl = -NCW * D + s - t;
-                if (dr >= 0 && dr <= M) {
-                    const uint32_t c = cv[G::T.run_of[dr - G::T.off_min]][s];
-                    pr = anyr ? pr + c : c;
-                    anyr = true;
-                }
-                if (dl < 0 && dl >= -M) {
-                    const uint32_t c = cv[G::T.run_of[dl - G::T.off_min]][s];
-                    pl = anyl ? pl + c : c;
-                    anyl = true;
-                }
-            }
-            if (D == DL) {
-                aR[t] = pr;
-                aL[t] = pl;
-            } else if (D == 0) {
+            if constexpr (anyr) pr = pR[w][D][t];
+            if constexpr (anyl) pl = pL[w][D][t];
+            if constexpr (D == DL) {
+                aR[w][t] = pr;
+                aL[w][t] = pl;
+            } else if constexpr (D == 0) {
                 // the last step and the final aR + aL as one plain add and two DPP adds: hop(aR) + (hop_up(aL) + (pr + pl))
                 uint32_t own = anyr && anyl ? pr + pl : anyr ? pr : pl;
                 asm("" : "+v"(own));
-                own = hop_up(aL[t]) + own;
+                own = hop_up(aL[w][t]) + own;
                 asm("" : "+v"(own));
-                aR[t] = hop(aR[t]) + own;  // the disc sum
-                asm("" : "+v"(aR[t]));     // (here, beside its DPP move, not sunk behind the caller's lane test)
+                aR[w][t] = hop(aR[w][t]) + own;  // the disc sum
+                asm("" : "+v"(aR[w][t]));        // (here, beside its DPP move, not sunk behind the caller's lane test)
             } else {
                 // (the lane's own part opaque: the DPP move folds into a two-operand add, see ring_disc_sum)
-                if (anyr) {
+                if constexpr (anyr) {
                     asm("" : "+v"(pr));
-                    aR[t] = hop(aR[t]) + pr;
+                    aR[w][t] = hop(aR[w][t]) + pr;
                 } else {
-                    aR[t] = hop(aR[t]);
+                    aR[w][t] = hop(aR[w][t]);
                 }
-                if (anyl) {
+                if constexpr (anyl) {
                     asm("" : "+v"(pl));
-                    aL[t] = hop_up(aL[t]) + pl;
+                    aL[w][t] = hop_up(aL[w][t]) + pl;
                 } else {
-                    aL[t] = hop_up(aL[t]);
+                    aL[w][t] = hop_up(aL[w][t]);
                 }
             }
-        }
+        });
         RING_SB();
-    }
+    };
+    wide_static_for<(LEAD < NR ? LEAD : NR)>([&](auto I) { fetch(I); });
+    if constexpr (PRIO) CHAIN_SETPRIO(3);
+    static_assert(DL >= 1 && G::S.first_step[G::S.order[0]] == DL, "the first run opens the chains, the last step (D = 0) closes both");
+    wide_static_for<NR>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        constexpr int r = G::S.order[j];
+        constexpr int D = G::S.first_step[r];  // the step that takes run r first (the steps go DL ... 0)
+        constexpr int Dprev = j == 0 ? DL : G::S.first_step[G::S.order[j > 0 ? j - 1 : 0]];
+        constexpr int Dnext = j + 1 < NR ? G::S.first_step[G::S.order[j + 1 < NR ? j + 1 : j]] : -1;
+        if constexpr (PRIO && SW_::prio_of(D) != SW_::prio_of(Dprev)) CHAIN_SETPRIO(SW_::prio_of(D));
+        if constexpr (j + LEAD < NR) fetch(std::integral_constant<int, j + LEAD>{});
+        RING_SB();
+        wide_static_for<NCW>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            uint32_t cv[2];
 #pragma unroll
-    for (int t = 0; t < NCW; ++t) {
-        acc[t] = aR[t];
-        ctr[t] = cv[G::S.centre_run][t];
-    }
+            for (int w = 0; w < 2; ++w) {
+                cv[w] = row[PT::T.use[j][w][0]][s / 2][s % 2] - row[PT::T.use[j][w][1]][s / 2][s % 2];
+                if (r == G::S.centre_run) ctr[w][s] = cv[w];
+            }
+            // every (step, output) that takes column s of run r: of this step and of the later ones
+            wide_static_for<(DL + 1) * NCW>([&](auto ET) {
+                constexpr int E = decltype(ET)::value / NCW, t = decltype(ET)::value % NCW;
+                constexpr int dr = NCW * E + s - t, dl = -NCW * E + s - t;
+                if constexpr (dr >= 0 && dr <= M) {
+                    if constexpr (G::T.run_of[dr - G::T.off_min] == r) {
+                        static_assert(E <= D, "a run arrives at the first step that takes it");
+#pragma unroll
+                        for (int w = 0; w < 2; ++w) pR[w][E][t] = SW_::T.firstR[E][t] == j * NCW + s ? cv[w] : pR[w][E][t] + cv[w];
+                    }
+                }
+                if constexpr (dl < 0 && dl >= -M) {
+                    if constexpr (G::T.run_of[dl - G::T.off_min] == r) {
+                        static_assert(E <= D, "a run arrives at the first step that takes it");
+#pragma unroll
+                        for (int w = 0; w < 2; ++w) pL[w][E][t] = SW_::T.firstL[E][t] == j * NCW + s ? cv[w] : pL[w][E][t] + cv[w];
+                    }
+                }
+            });
+        });
+        RING_SB();
+        // the steps no later run opens: closed here
+        wide_static_for<D - Dnext>([&](auto C) { close(std::integral_constant<int, D - decltype(C)::value>{}); });
+    });
+#pragma unroll
+    for (int w = 0; w < 2; ++w)
+#pragma unroll
+        for (int t = 0; t < NCW; ++t) acc[w][t] = aR[w][t];
 }
 
 
@@ -391,9 +472,16 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             hist = ((hist << 1) | (unsigned)all) & kHistMask;
         };
 
-        float2 va[B];
+        const int ocol = gx0 + lane * NCW;
+        const bool lane_ok = lane >= DL && lane < DL + G::NVL && ocol < p.nx;
         __syncthreads();  // (the previous run's chain waves are done with the ring and the flag words)
-        if (stager) {
+        // The run's prologue and phases, once for the staging waves and once for the chain waves: the same barriers on both
+        // sides, and the batch a staging wave holds in registers from one phase to the next (va) is no live value in the
+        // chain waves' loop, whose sweep needs those registers.
+        auto run_phases = [&](auto STG) {
+        constexpr bool stg = decltype(STG)::value;
+        float2 va[stg ? B : 1];
+        if constexpr (stg) {
             int bits = 0;
 #pragma unroll 1
             for (int k = 0; k < NB_PRO; ++k) {
@@ -414,8 +502,6 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             hist = (unsigned)__builtin_amdgcn_readfirstlane(all) & kHistMask;
         }
 
-        const int ocol = gx0 + lane * NCW;
-        const bool lane_ok = lane >= DL && lane < DL + G::NVL && ocol < p.nx;
         bool tile_frac = false;
 #pragma unroll 1
         for (int ph = 0; ph < nphase; ++ph) {
@@ -437,33 +523,37 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                 seen_frac += tile_frac ? 1 : 0;
                 tile_frac = false;
             }
-            if (stager) {
+            if constexpr (stg) {
                 // the batch phase ph + 1 needs, into the slots behind this phase's window; then the loads of the one after
                 const int seen = stage_batch(C::PRO + ph * B, va);
                 if (lane == 0) wflags[((ph + 1) & 1) * SW + wave] = seen;
                 load_batch(C::PRO + (ph + 1) * B, va);
             } else if (compute) {
-                static_assert(C::RPW == 2, "two rows per chain wave: the first and the second priority pair");
+                static_assert(C::RPW == 2, "a chain wave sums its two rows of a phase in one sweep");
+                const int j = (wave - SW) * C::RPW;  // first row of the pair in the phase
+                const int oy = oyA + j;
+                // A pair with a row in the output range is summed whole and the other row's store masked: no branch inside
+                // the sweep.  The masked row reads ring rows of this phase's window like its partner, and the staging has
+                // written the whole window of a phase that is computed (rows outside the raster as zeros).
+                if (oy + C::RPW > p.out_row0 && oy < p.out_row0 + p.out_rows) {
+                    const int s0 = (C::PAD - 1 + ph * B + j) % R;  // slot of Q index 0 of the first row's window
+                    uint32_t acc[C::RPW][NCW], ctr[C::RPW][NCW];
+                    wide_pair_sum<SIZE, R, C::GR, WIDE_LEAD, WIDE_PRIO != 0>(Q, s0, lane, acc, ctr);
 #pragma unroll
-                for (int k = 0; k < C::RPW; ++k) {
-                    const int j = (wave - SW) * C::RPW + k;  // row of the phase
-                    const int oy = oyA + j;
-                    if (oy < p.out_row0 || oy >= p.out_row0 + p.out_rows) continue;
-                    const int s0 = (C::PAD - 1 + ph * B + j) % R;  // slot of Q index 0 of the row's window
-                    uint32_t acc[NCW], ctr[NCW];
-                    if (k == 0) wide_disc_sum<SIZE, R, C::GR, WIDE_LEAD, true>(Q, s0, lane, acc, ctr);
-                    else wide_disc_sum<SIZE, R, C::GR, WIDE_LEAD, false>(Q, s0, lane, acc, ctr);
-                    if (lane_ok) {
-                        float* o = p.tpi + (size_t)(oy - p.out_row0) * p.nx + ocol;
-                        float out_t[NCW];
+                    for (int k = 0; k < C::RPW; ++k) {
+                        const bool row_ok = oy + k >= p.out_row0 && oy + k < p.out_row0 + p.out_rows;
+                        if (lane_ok && row_ok) {
+                            float* o = p.tpi + (size_t)(oy + k - p.out_row0) * p.nx + ocol;
+                            float out_t[NCW];
 #pragma unroll
-                        for (int t = 0; t < NCW; ++t) {
-                            const int xi = (int)ctr[t];  // integers: see tpi_march_kernel
-                            out_t[t] = (float)((double)xi - (double)((int)acc[t] - xi) * inv_nm1);
+                            for (int t = 0; t < NCW; ++t) {
+                                const int xi = (int)ctr[k][t];  // integers: see tpi_march_kernel
+                                out_t[t] = (float)((double)xi - (double)((int)acc[k][t] - xi) * inv_nm1);
+                            }
+#pragma unroll
+                            for (int P = 0; P < NCW / 2; ++P)  // (nx % 4 == 0, ocol even: a pair is inside or outside)
+                                if (ocol + 2 * P < p.nx) *reinterpret_cast<float2*>(o + 2 * P) = make_float2(out_t[2 * P], out_t[2 * P + 1]);
                         }
-#pragma unroll
-                        for (int P = 0; P < NCW / 2; ++P)  // (nx % 4 == 0, ocol even: a pair is inside or outside)
-                            if (ocol + 2 * P < p.nx) *reinterpret_cast<float2*>(o + 2 * P) = make_float2(out_t[2 * P], out_t[2 * P + 1]);
                     }
                 }
             }
@@ -471,6 +561,9 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             __syncthreads();
             fold((ph + 1) & 1);
         }
+        };
+        if (stager) run_phases(std::true_type{});
+        else run_phases(std::false_type{});
         pos += run_tiles;
     }
     if (p.report != nullptr && vb == nb / 2 && threadIdx.x == 0) {
