@@ -351,6 +351,66 @@ int topo_amd_valley_ridge_f32(const float* dem, int ny, int nx, const float* tap
                               int n_planes, double mean, double stdev, float* norm_out,
                               float* dir_out);
 
+/* ---- raw sources: a DEM uploaded as it is stored, decoded on the GPU ------------------------------------------------------
+ * SRTM and most GeoTIFF tiles are int16 with a nodata value, CF-packed netCDF is int16 / int32 with scale_factor,
+ * add_offset and _FillValue, xarray hands out float64.  A topo_amd_raster describes such an array; the *_raw entry points
+ * upload its bytes as they are and decode them to the float32 plane the kernels read, on the GPU, behind each row chunk's
+ * copy (csrc/decode.hip).  The decode, for a sample `raw` of the source type:
+ *
+ *     value = NaN                                       if has_nodata and (double)raw == nodata
+ *     value = (float) ( (double)raw * scale + offset )  otherwise
+ *
+ * The product and the sum are each rounded in float64 (never contracted into an FMA), the result is rounded to
+ * nearest-even to float32; NaN is 0x7FC00000.  With scale 1, offset 0 and no nodata this is numpy's astype(float32).  For
+ * float64 sources a NaN nodata means "none".  A nodata the source type cannot hold never matches.  A float32 source with
+ * scale 1, offset 0 and no nodata is passed through untouched (a copy: no decode runs, every bit is kept): the *_f32
+ * entry points are the *_raw ones called with such a source.  scale must be finite and not 0, offset finite, dtype one of
+ * the six below: anything else is TOPO_AMD_EINVAL.
+ * Every result is, bit for bit, that of the *_f32 call on the array topo_amd_decode_host gives: the raster class (above)
+ * is read off the decoded samples of the caller's array, chunks are cut by the float32 rows.                             */
+#define TOPO_AMD_F32 0
+#define TOPO_AMD_I16 1
+#define TOPO_AMD_U16 2
+#define TOPO_AMD_I32 3
+#define TOPO_AMD_U8 4
+#define TOPO_AMD_F64 5
+typedef struct topo_amd_raster {
+    const void* data; /* ny x nx samples of `dtype`, C-contiguous, native byte order */
+    int32_t dtype;    /* TOPO_AMD_F32 ... TOPO_AMD_F64 */
+    int32_t has_nodata;
+    double scale, offset, nodata;
+} topo_amd_raster;
+/* The formula above on the host, one thread: count samples of src->data -> out.  Needs no GPU and no topo_amd_init.      */
+int topo_amd_decode_host(const topo_amd_raster* src, size_t count, float* out);
+/* The same on the device, enqueued on the compute stream: count samples at raw_dev (aligned to the sample type) -> out_dev
+ * (any float-aligned address; 16-byte accesses where the two share a 16-byte phase, sample by sample otherwise).  Row
+ * shards hold device-resident blocks: they decode with this call.                                                        */
+int topo_amd_decode_dev(const void* raw_dev, int dtype, size_t count, double scale, double offset, int has_nodata,
+                        double nodata, float* out_dev);
+/* A host raster -> a float32 device plane [ny x nx]: uploaded in row chunks, each decoded while the next one is copied.
+ * Returns when the plane is complete (the source array is not retained).                                                 */
+int topo_amd_upload_raw(const topo_amd_raster* src, int ny, int nx, float* out_dev);
+/* The host-buffer entry points on a raw source: as their *_f32 namesakes with `src` in place of `dem`.                   */
+int topo_amd_tpi_raw(const topo_amd_raster* src, int ny, int nx, int size, double sigma, float* out);
+int topo_amd_std_raw(const topo_amd_raster* src, int ny, int nx, int size, double sigma, float* out);
+int topo_amd_tpi_std_raw(const topo_amd_raster* src, int ny, int nx, int size, double sigma, float* tpi_out, float* std_out);
+int topo_amd_tpi_std_multi_raw(const topo_amd_raster* src, int ny, int nx, int n_scales, const int32_t* sizes,
+                               const double* sigmas, float* const* tpi_outs, float* const* std_outs);
+int topo_amd_gauss_raw(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, float* out);
+int topo_amd_sobel_raw(const topo_amd_raster* src, int ny, int nx, float* dx_out, float* dy_out);
+int topo_amd_fill_na_raw(const topo_amd_raster* src, int ny, int nx, const double* x_coords, double min_elevation, float* out,
+                         uint8_t* missing_out);
+int topo_amd_gradient_raw(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
+                          const void* res_x, const void* res_y, float* dx_out, float* dy_out, float* slope_out,
+                          float* aspect_out);
+int topo_amd_sx_raw(const topo_amd_raster* src, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist,
+                    int n_off, int window, double height, float* out);
+int topo_amd_sx_multi_raw(const topo_amd_raster* src, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,
+                          const int32_t* di, const double* dist, const int32_t* window, double height, float* const* outs);
+int topo_amd_valley_ridge_raw(const topo_amd_raster* src, int ny, int nx, const float* taps, const int32_t* ksize,
+                              const float* angles, int n_angles, int n_planes, double mean, double stdev, float* norm_out,
+                              float* dir_out);
+
 /* ---- row sharding over the GPUs of one node (RCCL over xGMI) -------------------------- */
 /* The reference's only precedent is dask map_overlap(depth, boundary="none") for TPI
  * (topo.py:177-178): independent blocks plus ghost rows.  Rank r owns a contiguous row

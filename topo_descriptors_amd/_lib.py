@@ -14,6 +14,19 @@ _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
+
+class Raster(C.Structure):
+    """``topo_amd_raster`` (include/topo_amd.h): a raster as it is stored, and how its samples decode to float32."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("has_nodata", C.c_int32),
+                ("scale", C.c_double), ("offset", C.c_double), ("nodata", C.c_double)]
+
+
+_rp = C.POINTER(Raster)
+# numpy dtype -> TOPO_AMD_F32 ... TOPO_AMD_F64
+F32, I16, U16, I32, U8, F64 = range(6)
+SOURCE_DTYPES = {np.dtype(np.float32): F32, np.dtype(np.int16): I16, np.dtype(np.uint16): U16,
+                 np.dtype(np.int32): I32, np.dtype(np.uint8): U8, np.dtype(np.float64): F64}
+
 # name -> (restype, argtypes); every symbol include/topo_amd.h declares
 SIGNATURES = {
     "topo_amd_version": (C.c_char_p, []),
@@ -85,6 +98,24 @@ SIGNATURES = {
     "topo_amd_sx_f32": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _f64p, C.c_int, C.c_int,
                                   C.c_double, _vp]),
     "topo_amd_sx_multi_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _i32p,
+                                        C.c_double, C.POINTER(_vp)]),
+    "topo_amd_decode_host": (C.c_int, [_rp, C.c_size_t, _vp]),
+    "topo_amd_decode_dev": (C.c_int, [_vp, C.c_int, C.c_size_t, C.c_double, C.c_double, C.c_int, C.c_double, _vp]),
+    "topo_amd_upload_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp]),
+    "topo_amd_valley_ridge_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int,
+                                            C.c_double, C.c_double, _vp, _vp]),
+    "topo_amd_tpi_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
+    "topo_amd_std_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
+    "topo_amd_tpi_std_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp]),
+    "topo_amd_tpi_std_multi_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _vp, _vp]),
+    "topo_amd_gauss_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
+    "topo_amd_sobel_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp, _vp]),
+    "topo_amd_fill_na_raw": (C.c_int, [_rp, C.c_int, C.c_int, _f64p, C.c_double, _vp, _vp]),
+    "topo_amd_gradient_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
+    "topo_amd_sx_raw": (C.c_int, [_rp, C.c_int, C.c_int, _i32p, _i32p, _f64p, C.c_int, C.c_int,
+                                  C.c_double, _vp]),
+    "topo_amd_sx_multi_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _i32p,
                                         C.c_double, C.POINTER(_vp)]),
     "topo_amd_shard_sx_multi": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
                                           _i32p, _f64p, _i32p, C.c_double, C.POINTER(_vp)]),
@@ -174,3 +205,51 @@ def ptr(array):
 
 def as_f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def as_source(values, scale=1.0, offset=0.0, nodata=None):
+    """``(array, Raster)`` for the ``*_raw`` entry points: the array to keep alive for the call and the struct that points
+    into it.  Native-endian arrays of float32, int16, uint16, int32, uint8 and float64 go as they are stored (copied only
+    to make them C-contiguous; the dtype never changes) and are decoded on the GPU; anything else (int64, float16, bool,
+    byte-swapped, object) is cast to float32 on the host first, as :func:`as_f32` does."""
+    a = np.asarray(values)
+    if a.dtype in SOURCE_DTYPES and a.dtype.isnative:
+        a = np.ascontiguousarray(a)
+    else:
+        a = as_f32(a)
+    raster = Raster(a.ctypes.data, SOURCE_DTYPES[a.dtype], int(nodata is not None), float(scale), float(offset),
+                    0.0 if nodata is None else float(nodata))
+    return a, raster
+
+
+class PackedDem:
+    """A DEM as a file stores it - ``values`` of any dtype with CF's ``scale_factor``, ``add_offset`` and ``_FillValue`` -
+    for every ``topo.*`` function that takes an ndarray: the samples are uploaded as stored and decoded on the GPU
+    (include/topo_amd.h, "raw sources": ``fill_value`` becomes NaN, every other sample ``float32(float64(raw) *
+    scale_factor + add_offset)``).  What it decodes to is float32: ``dtype`` says so, whatever ``values.dtype`` is."""
+
+    def __init__(self, values, scale_factor=1.0, add_offset=0.0, fill_value=None):
+        self.values = np.asarray(values)
+        self.scale_factor = float(scale_factor)
+        self.add_offset = float(add_offset)
+        self.fill_value = None if fill_value is None else float(fill_value)
+        self.shape = self.values.shape
+        self.ndim = self.values.ndim
+        self.dtype = np.dtype(np.float32)
+
+    def source(self):
+        return as_source(self.values, self.scale_factor, self.add_offset, self.fill_value)
+
+    def decode(self):
+        """The float32 array the GPU decodes to, computed on the host (``topo_amd_decode_host``; one thread)."""
+        a, raster = self.source()
+        out = np.empty(a.shape, dtype=np.float32)
+        check(load().topo_amd_decode_host(C.byref(raster), a.size, ptr(out)), "topo_amd_decode_host")
+        return out
+
+
+def source_of(values):
+    """:func:`as_source` of an ndarray or a :class:`PackedDem`."""
+    if isinstance(values, PackedDem):
+        return values.source()
+    return as_source(values)

@@ -81,10 +81,19 @@ class _ResidentDem:
     """The DEM on the GPU for the duration of one wrapper call."""
 
     def __init__(self, dem_val):
-        self.host = _lib.as_f32(dem_val)
-        self.dev = d.DeviceArray.from_host(self.host)
+        self.source = dem_val if isinstance(dem_val, _lib.PackedDem) else np.asarray(dem_val)
+        self.dev = d.DeviceArray.from_host(self.source)  # as stored: decoded on the GPU
         self.block = d.Block(self.dev)
-        self.shape = self.host.shape
+        self.shape = (self.dev.rows, self.dev.nx)
+        self._host = None
+
+    @property
+    def host(self):
+        """The float32 array on the host, made when somebody asks (the un-smoothed valley / ridge index: numpy's mean and
+        std): the plane the GPU decoded."""
+        if self._host is None:
+            self._host = self.dev.to_host()
+        return self._host
 
     def plane(self):
         return d.DeviceArray(*self.shape)

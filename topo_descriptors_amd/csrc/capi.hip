@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "decode.hpp"
 
 #include <sys/mman.h>
 
@@ -319,12 +320,19 @@ int scan_block(const Block& b, int own_row0, int own_rows, Scan* out) {
     }
     return TOPO_AMD_OK;
 }
-// the same lattice on a host array (the host-buffer entry points: no launch, no synchronisation)
-RasterClass scan_host(const float* dem, int ny, int nx) {
+// the same lattice on a host array (the host-buffer entry points: no launch, no synchronisation), each sample decoded
+// as the device will decode it (decode.hpp): the class is that of the float32 plane the kernels read
+// (kAsStored: a float32 source that goes to the device untouched is classified on its own bits)
+template <bool kAsStored, class T>
+RasterClass scan_host(const T* dem, const DecodeParams& p, int ny, int nx) {
     Scan s;
     const int step_r = lattice_step(ny), step_c = lattice_step(nx);
     for (int r = step_r / 2; r < ny; r += step_r)
-        for (int c = step_c / 2; c < nx; c += step_c) s.add(dem[(size_t)r * nx + c]);
+        for (int c = step_c / 2; c < nx; c += step_c) {
+            const T x = dem[(size_t)r * nx + c];
+            if constexpr (kAsStored) s.add((float)x);
+            else s.add(decode_host(x, p));
+        }
     return class_of(s);
 }
 
@@ -643,18 +651,75 @@ std::vector<int> pipeline_cuts(int ny, int chunk) {
 // compute(view_rows, out_row0, out_rows): enqueue the kernels that write output rows [out_row0, out_row0 + out_rows) of
 // every plane, reading rows [0, view_rows) of d_in.  above / below: rows of the DEM an output row depends on.
 // upload == false: the DEM is on the device already (later scales of a multi-scale call).
+// The caller's raster as a host-buffer call sees it: a checked topo_amd_raster.  as_stored: float32 that needs no decode (the
+// *_f32 path: copied straight into the float32 plane, no raw plane, no decode launch).
+struct Source {
+    const char* data = nullptr;
+    int dtype = TOPO_AMD_F32;
+    size_t elem = sizeof(float);
+    DecodeParams p;
+    bool as_stored = true;
+    const char* row(int r, int nx) const { return data + (size_t)r * nx * elem; }
+};
+int make_source(const topo_amd_raster* r, const char* who, Source* s) {
+    TOPO_REQUIRE(r != nullptr && r->data != nullptr, "%s: bad DEM", who);
+    s->elem = sample_bytes(r->dtype);
+    TOPO_REQUIRE(s->elem != 0, "%s: unknown sample type %d (TOPO_AMD_F32 ... TOPO_AMD_F64)", who, (int)r->dtype);
+    TOPO_REQUIRE(std::isfinite(r->scale) && r->scale != 0.0, "%s: scale %g (it must be finite and not 0)", who, r->scale);
+    TOPO_REQUIRE(std::isfinite(r->offset), "%s: offset %g is not finite", who, r->offset);
+    s->data = (const char*)r->data;
+    s->dtype = r->dtype;
+    s->p.scale = r->scale;
+    s->p.offset = r->offset;
+    s->p.has_nodata = r->has_nodata != 0 && !std::isnan(r->nodata);  // (NaN equals nothing: "none")
+    s->p.nodata = s->p.has_nodata ? r->nodata : 0.0;
+    s->as_stored = r->dtype == TOPO_AMD_F32 && r->scale == 1.0 && r->offset == 0.0 && !s->p.has_nodata;
+    return TOPO_AMD_OK;
+}
+topo_amd_raster f32_raster(const float* dem) { return topo_amd_raster{dem, TOPO_AMD_F32, 0, 1.0, 0.0, 0.0}; }
+RasterClass scan_source(const Source& s, int ny, int nx) {
+    RasterClass cls;
+    if (s.as_stored) return scan_host<true>((const float*)s.data, s.p, ny, nx);
+    with_sample_type(s.dtype, [&](auto t) { cls = scan_host<false>((const decltype(t)*)s.data, s.p, ny, nx); });
+    return cls;
+}
+// rows [r0, r1) of the source -> the same rows of the float32 plane d_in, enqueued on `stream`: a copy, or a copy into the
+// raw plane d_raw and the decode behind it
+hipError_t enqueue_rows(const Source& s, char* d_raw, float* d_in, int r0, int r1, int nx, hipStream_t stream) {
+    const size_t count = (size_t)(r1 - r0) * nx;
+    if (s.as_stored) return hipMemcpyAsync(d_in + (size_t)r0 * nx, s.row(r0, nx), count * sizeof(float), hipMemcpyHostToDevice, stream);
+    char* raw = d_raw + (size_t)r0 * nx * s.elem;
+    hipError_t e = hipMemcpyAsync(raw, s.row(r0, nx), count * s.elem, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    if (launch_decode(stream, raw, s.dtype, count, s.p, d_in + (size_t)r0 * nx) != TOPO_AMD_OK) return hipErrorLaunchFailure;
+    return hipSuccess;
+}
+// the raw plane of a call (nullptr for a source that needs none): the LAST plane a call takes from the pool, so the planes
+// of a float32 call are the ones they always were
+int raw_plane(HostRun& run, const Source& s, int ny, int nx, char** d_raw) {
+    *d_raw = nullptr;
+    if (s.as_stored) return TOPO_AMD_OK;
+    void* p = nullptr;
+    TOPO_TRY(run.alloc(&p, (size_t)ny * nx * s.elem));
+    *d_raw = (char*)p;
+    return TOPO_AMD_OK;
+}
+
+// src: the caller's raster (ignored when upload == false).  A source that is not float32-as-stored goes chunk by chunk into
+// a raw device plane and is decoded into d_in on the stream of the copy, in front of the event the kernels wait for.
 template <class Compute>
-int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, int above, int below, bool upload,
+int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, int above, int below, bool upload,
                   const std::vector<HostPlane>& outs, Compute&& compute) {
     Context& c = ctx();
+    char* d_raw = nullptr;
+    if (upload) TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
     const int chunk = pipeline_chunk_rows(ny, nx);
     const std::vector<int> cut = chunk >= ny ? std::vector<int>{0, ny} : pipeline_cuts(ny, chunk);
     const int nchunks = (int)cut.size() - 1;
-    const size_t row_bytes = (size_t)nx * sizeof(float);
     (void)above;
     t_host_chunks = std::max(t_host_chunks, nchunks < 3 ? 1 : nchunks);  // (a multi-scale call: the most any of its scales ran in)
     if (nchunks < 3) {
-        if (upload) TOPO_HIP(hipMemcpyAsync(d_in, dem, (size_t)ny * row_bytes, hipMemcpyHostToDevice, c.compute));
+        if (upload) TOPO_HIP(enqueue_rows(src, d_raw, d_in, 0, ny, nx, c.compute));
         const int rc = compute(ny, 0, ny);
         if (rc != TOPO_AMD_OK && rc != TOPO_AMD_EEMPTY) return rc;
         run.ready();
@@ -690,7 +755,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
         }
         return attr.type == hipMemoryTypeHost;
     };
-    bool all_locked = !upload || page_locked(dem);
+    bool all_locked = !upload || page_locked(src.data);
     for (const HostPlane& o : outs) all_locked = all_locked && page_locked(o.host);
     const bool inline_downloads = forced_mode == 2 || (forced_mode == 0 && all_locked);
     std::mutex mu;
@@ -738,8 +803,7 @@ int run_pipelined(HostRun& run, const float* dem, float* d_in, int ny, int nx, i
     for (int k = 0; k < nchunks && rc == TOPO_AMD_OK; ++k) {
         const int u0 = cut[k], u1 = cut[k + 1];
         if (upload) {
-            hipError_t e = hipMemcpyAsync(d_in + (size_t)u0 * nx, dem + (size_t)u0 * nx, (size_t)(u1 - u0) * row_bytes,
-                                          hipMemcpyHostToDevice, c.up);
+            hipError_t e = enqueue_rows(src, d_raw, d_in, u0, u1, nx, c.up);
             if (e == hipSuccess) e = hipEventRecord(up_done[k], c.up);
             if (e != hipSuccess) {
                 set_error("upload of a row chunk failed: %s", hipGetErrorString(e));
@@ -1513,14 +1577,16 @@ int topo_amd_fill_na_dev(const float* in, int in_rows, int in_row0, int gny, int
 }
 
 // ---- host-buffer entry points ----------------------------------------------------------------
-int topo_amd_tpi_std_f32(const float* dem, int ny, int nx, int size, double sigma, float* tpi_out,
+int topo_amd_tpi_std_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* tpi_out,
                          float* std_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && ny >= 1 && nx >= 1, "tpi_std: bad DEM");
+    Source src;
+    TOPO_TRY(make_source(raster, "tpi_std", &src));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std: bad DEM");
     TOPO_REQUIRE(tpi_out || std_out, "tpi_std: both outputs are NULL");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_host(dem, ny, nx));  // the raster class from the caller's array: no launch, no synchronisation
+    ClassScope cls(scan_source(src, ny, nx));  // the raster class from the caller's array: no launch, no synchronisation
     int above = 0, below = 0;
     TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)size, sigma, &above, &below));
     HostRun run;
@@ -1530,18 +1596,20 @@ int topo_amd_tpi_std_f32(const float* dem, int ny, int nx, int size, double sigm
     if (std_out) TOPO_TRY(run.alloc(&d_std, bytes));
     run.prefault(tpi_out, bytes);
     run.prefault(std_out, bytes);
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, above, below, true, {{tpi_out, (float*)d_tpi}, {std_out, (float*)d_std}},
+    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {{tpi_out, (float*)d_tpi}, {std_out, (float*)d_std}},
                          [&](int view_rows, int r0, int rows) {
                              Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
                              return tpi_std_block(b, size, sigma, shift((float*)d_tpi, r0, nx), shift((float*)d_std, r0, nx));
                          });
 }
 
-int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, const int32_t* sizes,
+int topo_amd_tpi_std_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_scales, const int32_t* sizes,
                                const double* sigmas, float* const* tpi_outs, float* const* std_outs) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && ny >= 1 && nx >= 1, "tpi_std_multi: bad DEM");
+    Source src;
+    TOPO_TRY(make_source(raster, "tpi_std_multi", &src));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std_multi: bad DEM");
     TOPO_REQUIRE(n_scales >= 1 && sizes, "tpi_std_multi: no scales");
     TOPO_REQUIRE(tpi_outs || std_outs, "tpi_std_multi: both output lists are NULL");
     bool any_tpi = false, any_std = false;
@@ -1552,7 +1620,7 @@ int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, c
         any_std |= s;
     }
     const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_host(dem, ny, nx));
+    ClassScope cls(scan_source(src, ny, nx));
     HostRun run;
     void *d_in = nullptr, *d_tpi = nullptr, *d_std = nullptr;
     TOPO_TRY(run.alloc(&d_in, bytes));
@@ -1569,7 +1637,7 @@ int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, c
         float* sd = std_outs && std_outs[k] ? (float*)d_std : nullptr;
         int above = 0, below = 0;
         TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)sizes[k], sigmas ? sigmas[k] : 0.0, &above, &below));
-        TOPO_TRY(run_pipelined(run, dem, (float*)d_in, ny, nx, above, below, k == 0,
+        TOPO_TRY(run_pipelined(run, src, (float*)d_in, ny, nx, above, below, k == 0,
                                {{t ? tpi_outs[k] : nullptr, t}, {sd ? std_outs[k] : nullptr, sd}}, [&](int view_rows, int r0, int rows) {
                                    Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
                                    return tpi_std_block(b, sizes[k], sigmas ? sigmas[k] : 0.0, shift(t, r0, nx), shift(sd, r0, nx));
@@ -1578,25 +1646,27 @@ int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, c
     return TOPO_AMD_OK;
 }
 
-int topo_amd_tpi_f32(const float* dem, int ny, int nx, int size, double sigma, float* out) {
+int topo_amd_tpi_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* out) {
     TOPO_ENTER();
     TOPO_REQUIRE(out != nullptr, "tpi: NULL output");
-    return topo_amd_tpi_std_f32(dem, ny, nx, size, sigma, out, nullptr);
+    return topo_amd_tpi_std_raw(raster, ny, nx, size, sigma, out, nullptr);
 }
 
-int topo_amd_std_f32(const float* dem, int ny, int nx, int size, double sigma, float* out) {
+int topo_amd_std_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* out) {
     TOPO_ENTER();
     TOPO_REQUIRE(out != nullptr, "std: NULL output");
-    return topo_amd_tpi_std_f32(dem, ny, nx, size, sigma, nullptr, out);
+    return topo_amd_tpi_std_raw(raster, ny, nx, size, sigma, nullptr, out);
 }
 
-int topo_amd_gauss_f32(const float* dem, int ny, int nx, double sigma_y, double sigma_x, float* out) {
+int topo_amd_gauss_raw(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, float* out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && out && ny >= 1 && nx >= 1, "gauss: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "gauss", &src));
+    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "gauss: bad arguments");
     TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gaussian: negative sigma");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_host(dem, ny, nx));
+    ClassScope cls(scan_source(src, ny, nx));
     int above = 0, below = 0;
     TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_GAUSS, sigma_y, 0.0, &above, &below));
     HostRun run;
@@ -1604,15 +1674,17 @@ int topo_amd_gauss_f32(const float* dem, int ny, int nx, double sigma_y, double 
     TOPO_TRY(run.alloc(&d_in, bytes));
     TOPO_TRY(run.alloc(&d_out, bytes));
     run.prefault(out, bytes);
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, above, below, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
+    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
         return topo_amd_gaussian_dev((const float*)d_in, view_rows, 0, ny, nx, sigma_y, sigma_x, r0, rows, shift((float*)d_out, r0, nx));
     });
 }
 
-int topo_amd_sobel_f32(const float* dem, int ny, int nx, float* dx_out, float* dy_out) {
+int topo_amd_sobel_raw(const topo_amd_raster* raster, int ny, int nx, float* dx_out, float* dy_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && dx_out && dy_out && ny >= 1 && nx >= 1, "sobel: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "sobel", &src));
+    TOPO_REQUIRE(dx_out && dy_out && ny >= 1 && nx >= 1, "sobel: bad arguments");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
     HostRun run;
     void *d_in = nullptr, *d_dx = nullptr, *d_dy = nullptr;
@@ -1621,18 +1693,20 @@ int topo_amd_sobel_f32(const float* dem, int ny, int nx, float* dx_out, float* d
     TOPO_TRY(run.alloc(&d_dy, bytes));
     run.prefault(dx_out, bytes);
     run.prefault(dy_out, bytes);
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, 1, 1, true, {{dx_out, (float*)d_dx}, {dy_out, (float*)d_dy}},
+    return run_pipelined(run, src, (float*)d_in, ny, nx, 1, 1, true, {{dx_out, (float*)d_dx}, {dy_out, (float*)d_dy}},
                          [&](int view_rows, int r0, int rows) {
                              return topo_amd_sobel_dev((const float*)d_in, view_rows, 0, ny, nx, r0, rows, shift((float*)d_dx, r0, nx),
                                                        shift((float*)d_dy, r0, nx));
                          });
 }
 
-int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coords, double min_elevation, float* out,
+int topo_amd_fill_na_raw(const topo_amd_raster* raster, int ny, int nx, const double* x_coords, double min_elevation, float* out,
                          uint8_t* missing_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && out && ny >= 1 && nx >= 1, "fill_na: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "fill_na", &src));
+    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "fill_na: bad arguments");
     bool ascending = true;
     TOPO_TRY(check_fill_coords(x_coords, nx, &ascending));  // (before anything moves)
     const size_t bytes = (size_t)ny * nx * sizeof(float), mask_bytes = (size_t)ny * nx;
@@ -1642,7 +1716,7 @@ int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coord
     if (missing_out) TOPO_TRY(run.alloc(&d_miss, mask_bytes));
     run.prefault(out, bytes);
     run.prefault(missing_out, mask_bytes);
-    return run_pipelined(run, dem, (float*)d_plane, ny, nx, 0, 0, true, {{out, d_plane}, {missing_out, d_miss, 1}},
+    return run_pipelined(run, src, (float*)d_plane, ny, nx, 0, 0, true, {{out, d_plane}, {missing_out, d_miss, 1}},
                          [&](int view_rows, int r0, int rows) {
                              return topo_amd_fill_na_dev((const float*)d_plane, view_rows, 0, ny, nx, x_coords, min_elevation, r0, rows,
                                                          shift((float*)d_plane, r0, nx),
@@ -1650,14 +1724,16 @@ int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coord
                          });
 }
 
-int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double sig_ratio,
+int topo_amd_gradient_raw(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio,
                           int res_mode, const void* res_x, const void* res_y, float* dx_out,
                           float* dy_out, float* slope_out, float* aspect_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && ny >= 1 && nx >= 1, "gradient: bad DEM");
+    Source src;
+    TOPO_TRY(make_source(raster, "gradient", &src));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1, "gradient: bad DEM");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_host(dem, ny, nx));
+    ClassScope cls(scan_source(src, ny, nx));
     HostRun run;
     void *d_in = nullptr, *d_o[4] = {nullptr, nullptr, nullptr, nullptr};
     float* host_out[4] = {dx_out, dy_out, slope_out, aspect_out};
@@ -1679,7 +1755,7 @@ int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double
     const int h = gradient_ghost_rows(sigma, sig_ratio, true);
     std::vector<HostPlane> outs;
     for (int k = 0; k < 4; ++k) outs.push_back({host_out[k], (float*)d_o[k]});
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, h, h, true, outs, [&](int view_rows, int r0, int rows) {
+    return run_pipelined(run, src, (float*)d_in, ny, nx, h, h, true, outs, [&](int view_rows, int r0, int rows) {
         const void *cx = rx, *cy = ry;
         if (res_mode == TOPO_AMD_RES_2D) {  // [out_rows x nx], aligned with the output rows
             cx = (const float*)rx + (size_t)r0 * nx;
@@ -1691,11 +1767,13 @@ int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double
     });
 }
 
-int topo_amd_sx_f32(const float* dem, int ny, int nx, const int32_t* dj, const int32_t* di,
+int topo_amd_sx_raw(const topo_amd_raster* raster, int ny, int nx, const int32_t* dj, const int32_t* di,
                     const double* dist, int n_off, int window, double height, float* out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && out && ny >= 1 && nx >= 1, "sx: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "sx", &src));
+    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "sx: bad arguments");
     // (no ray pixel at all: the tables may be NULL; the plane is zero-filled and the call answers TOPO_AMD_EEMPTY, like
     // a sector whose pixels are all NaN)
     TOPO_REQUIRE(n_off >= 0 && (n_off == 0 || (dj && di && dist)), "sx: NULL argument");
@@ -1711,18 +1789,20 @@ int topo_amd_sx_f32(const float* dem, int ny, int nx, const int32_t* dj, const i
     TOPO_TRY(run.alloc(&d_in, bytes));
     TOPO_TRY(run.alloc(&d_out, bytes));
     run.prefault(out, bytes);
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, up, down, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
+    return run_pipelined(run, src, (float*)d_in, ny, nx, up, down, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
         return topo_amd_sx_dev((const float*)d_in, view_rows, 0, ny, nx, dj, di, dist, n_off, window, height, r0, rows,
                                shift((float*)d_out, r0, nx));
     });
 }
 
-int topo_amd_sx_multi_f32(const float* dem, int ny, int nx, int n_az, const int32_t* first,
+int topo_amd_sx_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_az, const int32_t* first,
                           const int32_t* dj, const int32_t* di, const double* dist, const int32_t* window,
                           double height, float* const* outs) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && outs && n_az >= 1 && ny >= 1 && nx >= 1, "sx_multi: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "sx_multi", &src));
+    TOPO_REQUIRE(outs && n_az >= 1 && ny >= 1 && nx >= 1, "sx_multi: bad arguments");
     TOPO_REQUIRE(first && dj && di && dist && window, "sx_multi: NULL argument");
     for (int k = 0; k < n_az; ++k) TOPO_REQUIRE(outs[k], "sx_multi: NULL output plane %d", k);
     const size_t bytes = (size_t)ny * nx * sizeof(float);
@@ -1737,19 +1817,21 @@ int topo_amd_sx_multi_f32(const float* dem, int ny, int nx, int n_az, const int3
     std::vector<HostPlane> planes;
     for (int k = 0; k < n_az; ++k) planes.push_back({outs[k], d_out[k]});
     std::vector<float*> moved(n_az);
-    return run_pipelined(run, dem, (float*)d_in, ny, nx, up, down, true, planes, [&](int view_rows, int r0, int rows) {
+    return run_pipelined(run, src, (float*)d_in, ny, nx, up, down, true, planes, [&](int view_rows, int r0, int rows) {
         for (int k = 0; k < n_az; ++k) moved[k] = shift(d_out[k], r0, nx);
         return topo_amd_sx_multi_dev((const float*)d_in, view_rows, 0, ny, nx, n_az, first, dj, di, dist, window, height, r0, rows,
                                      moved.data());  // (EEMPTY: every plane was written)
     });
 }
 
-int topo_amd_valley_ridge_f32(const float* dem, int ny, int nx, const float* taps, const int32_t* ksize,
+int topo_amd_valley_ridge_raw(const topo_amd_raster* raster, int ny, int nx, const float* taps, const int32_t* ksize,
                               const float* angles, int n_angles, int n_planes, double mean, double stdev,
                               float* norm_out, float* dir_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    TOPO_REQUIRE(dem && ny >= 1 && nx >= 1 && norm_out && dir_out, "valley_ridge: bad arguments");
+    Source src;
+    TOPO_TRY(make_source(raster, "valley_ridge", &src));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1 && norm_out && dir_out, "valley_ridge: bad arguments");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
     HostRun run;
     void *d_in = nullptr, *d_norm = nullptr, *d_dir = nullptr;
@@ -1761,7 +1843,9 @@ int topo_amd_valley_ridge_f32(const float* dem, int ny, int nx, const float* tap
     // (not pipelined: half a second of kernels per 20 ms of copies at full size, and the FFT route of the large kernels is
     // not cut-invariant)
     t_host_chunks = 1;
-    TOPO_HIP(hipMemcpyAsync(d_in, dem, bytes, hipMemcpyHostToDevice, ctx().compute));
+    char* d_raw = nullptr;
+    TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    TOPO_HIP(enqueue_rows(src, d_raw, (float*)d_in, 0, ny, nx, ctx().compute));
     TOPO_TRY(topo_amd_valley_ridge_dev((const float*)d_in, ny, 0, ny, nx, taps, ksize, angles, n_angles, n_planes,
                                        mean, stdev, 0, ny, (float*)d_norm, (float*)d_dir));
     run.ready();
@@ -1769,6 +1853,137 @@ int topo_amd_valley_ridge_f32(const float* dem, int ny, int nx, const float* tap
     TOPO_TRY(download(dir_out, d_dir, bytes));
     TOPO_HIP(hipStreamSynchronize(ctx().compute));
     return TOPO_AMD_OK;
+}
+
+// ---- the *_f32 entry points: the *_raw ones on float32 as stored -------------------------------------------------------------
+int topo_amd_tpi_f32(const float* dem, int ny, int nx, int size, double sigma, float* out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_tpi_raw(&r, ny, nx, size, sigma, out);
+}
+int topo_amd_std_f32(const float* dem, int ny, int nx, int size, double sigma, float* out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_std_raw(&r, ny, nx, size, sigma, out);
+}
+int topo_amd_tpi_std_f32(const float* dem, int ny, int nx, int size, double sigma, float* tpi_out, float* std_out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_tpi_std_raw(&r, ny, nx, size, sigma, tpi_out, std_out);
+}
+int topo_amd_tpi_std_multi_f32(const float* dem, int ny, int nx, int n_scales, const int32_t* sizes, const double* sigmas,
+                               float* const* tpi_outs, float* const* std_outs) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_tpi_std_multi_raw(&r, ny, nx, n_scales, sizes, sigmas, tpi_outs, std_outs);
+}
+int topo_amd_gauss_f32(const float* dem, int ny, int nx, double sigma_y, double sigma_x, float* out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_gauss_raw(&r, ny, nx, sigma_y, sigma_x, out);
+}
+int topo_amd_sobel_f32(const float* dem, int ny, int nx, float* dx_out, float* dy_out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_sobel_raw(&r, ny, nx, dx_out, dy_out);
+}
+int topo_amd_fill_na_f32(const float* dem, int ny, int nx, const double* x_coords, double min_elevation, float* out,
+                         uint8_t* missing_out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_fill_na_raw(&r, ny, nx, x_coords, min_elevation, out, missing_out);
+}
+int topo_amd_gradient_f32(const float* dem, int ny, int nx, double sigma, double sig_ratio, int res_mode, const void* res_x,
+                          const void* res_y, float* dx_out, float* dy_out, float* slope_out, float* aspect_out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_gradient_raw(&r, ny, nx, sigma, sig_ratio, res_mode, res_x, res_y, dx_out, dy_out, slope_out, aspect_out);
+}
+int topo_amd_sx_f32(const float* dem, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist, int n_off,
+                    int window, double height, float* out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_sx_raw(&r, ny, nx, dj, di, dist, n_off, window, height, out);
+}
+int topo_amd_sx_multi_f32(const float* dem, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj, const int32_t* di,
+                          const double* dist, const int32_t* window, double height, float* const* outs) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_sx_multi_raw(&r, ny, nx, n_az, first, dj, di, dist, window, height, outs);
+}
+int topo_amd_valley_ridge_f32(const float* dem, int ny, int nx, const float* taps, const int32_t* ksize, const float* angles,
+                              int n_angles, int n_planes, double mean, double stdev, float* norm_out, float* dir_out) {
+    const topo_amd_raster r = f32_raster(dem);
+    return topo_amd_valley_ridge_raw(&r, ny, nx, taps, ksize, angles, n_angles, n_planes, mean, stdev, norm_out, dir_out);
+}
+
+// ---- the decode on its own ---------------------------------------------------------------------------------------------------
+int topo_amd_decode_host(const topo_amd_raster* raster, size_t count, float* out) {
+    Source src;  // (no GPU, no context: nothing to lock)
+    TOPO_TRY(make_source(raster, "decode_host", &src));
+    TOPO_REQUIRE(out != nullptr || count == 0, "decode_host: NULL output");
+    if (src.as_stored) {
+        if (count) std::memcpy(out, src.data, count * sizeof(float));
+        return TOPO_AMD_OK;
+    }
+    return decode_host_array(src.data, src.dtype, count, src.p, out);
+}
+
+int topo_amd_decode_dev(const void* raw_dev, int dtype, size_t count, double scale, double offset, int has_nodata, double nodata,
+                        float* out_dev) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    const topo_amd_raster r{raw_dev, dtype, has_nodata, scale, offset, nodata};
+    Source src;
+    TOPO_TRY(make_source(&r, "decode_dev", &src));
+    TOPO_REQUIRE(out_dev != nullptr, "decode_dev: NULL output");
+    dem_memo_forget(out_dev, count * sizeof(float));
+    if (count == 0) return TOPO_AMD_OK;
+    if (src.as_stored) {
+        if ((const void*)out_dev != raw_dev)
+            TOPO_HIP(hipMemcpyAsync(out_dev, raw_dev, count * sizeof(float), hipMemcpyDeviceToDevice, ctx().compute));
+        return TOPO_AMD_OK;
+    }
+    return launch_decode(ctx().compute, raw_dev, dtype, count, src.p, out_dev);
+}
+
+int topo_amd_upload_raw(const topo_amd_raster* raster, int ny, int nx, float* out_dev) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    Source src;
+    TOPO_TRY(make_source(raster, "upload_raw", &src));
+    TOPO_REQUIRE(out_dev && ny >= 1 && nx >= 1, "upload_raw: bad arguments");
+    Context& c = ctx();
+    dem_memo_forget(out_dev, (size_t)ny * nx * sizeof(float));
+    HostRun run(false);
+    char* d_raw = nullptr;
+    TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    // the copies on the upload stream, each chunk's decode on the compute stream behind its copy: chunk k is decoded while
+    // chunk k + 1 crosses the link (float32 as stored: nothing to decode, one copy)
+    const int chunk = src.as_stored ? ny : pipeline_chunk_rows(ny, nx);
+    const std::vector<int> cut = chunk >= ny ? std::vector<int>{0, ny} : pipeline_cuts(ny, chunk);
+    const int nchunks = (int)cut.size() - 1;
+    if (nchunks == 1) {
+        TOPO_HIP(enqueue_rows(src, d_raw, out_dev, 0, ny, nx, c.compute));
+        TOPO_HIP(hipStreamSynchronize(c.compute));
+        return TOPO_AMD_OK;
+    }
+    if (!c.up) {
+        TOPO_HIP(hipStreamCreateWithFlags(&c.up, hipStreamNonBlocking));
+        TOPO_HIP(hipStreamCreateWithFlags(&c.down, hipStreamNonBlocking));
+    }
+    while ((int)c.pipe_events.size() < nchunks) {
+        hipEvent_t e = nullptr;
+        TOPO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c.pipe_events.push_back(e);
+    }
+    TOPO_HIP(hipStreamSynchronize(c.compute));  // (whatever still reads or writes the plane is over before the copies start)
+    int rc = TOPO_AMD_OK;
+    for (int k = 0; k < nchunks && rc == TOPO_AMD_OK; ++k) {
+        const size_t at = (size_t)cut[k] * nx, count = (size_t)(cut[k + 1] - cut[k]) * nx;
+        hipError_t e = hipMemcpyAsync(d_raw + at * src.elem, src.row(cut[k], nx), count * src.elem, hipMemcpyHostToDevice, c.up);
+        if (e == hipSuccess) e = hipEventRecord(c.pipe_events[k], c.up);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c.compute, c.pipe_events[k], 0);
+        if (e != hipSuccess) {
+            set_error("upload of a row chunk failed: %s", hipGetErrorString(e));
+            rc = TOPO_AMD_EHIP;
+            break;
+        }
+        rc = launch_decode(c.compute, d_raw + at * src.elem, src.dtype, count, src.p, out_dev + at);
+    }
+    (void)hipStreamSynchronize(c.up);
+    (void)hipStreamSynchronize(c.compute);
+    return rc;
 }
 
 // ---- RCCL row sharding ------------------------------------------------------------------------

@@ -26,9 +26,11 @@ class DeviceArray:
 
     @classmethod
     def from_host(cls, array):
-        a = _lib.as_f32(array)
+        """A float32 plane from an ndarray or ``PackedDem``: supported dtypes are uploaded as stored, in row chunks, and decoded
+        on the GPU while the next chunk is copied (``topo_amd_upload_raw``)."""
+        a, raster = _lib.source_of(array)
         d = cls(a.shape[0], a.shape[1])
-        _lib.check(_lib.lib().topo_amd_memcpy_h2d(d.ptr, _lib.ptr(a), d.nbytes), "memcpy_h2d")
+        _lib.check(_lib.lib().topo_amd_upload_raw(C.byref(raster), a.shape[0], a.shape[1], d.ptr), "upload_raw")
         return d
 
     def row_ptr(self, row):

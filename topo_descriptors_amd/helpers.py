@@ -234,7 +234,7 @@ def _fill_coords(x_coords, nx):
 
 def fill_na_gpu(values, x_coords=None, min_elevation=None):
     """``(missing, filled)``: what the reference's ``fill_na`` returns as ``(ind_nans, filled)`` (helpers.py:137-154),
-    computed on the GPU (``topo_amd_fill_na_f32``) with the bits of :func:`fill_na_array`.  A sample is missing when it is
+    computed on the GPU (``topo_amd_fill_na_raw``) with the bits of :func:`fill_na_array`.  A sample is missing when it is
     NaN or, with ``min_elevation``, at or below it (float32 comparison: the masking of ``get_dem_netcdf``, helpers.py:30-31);
     each is replaced by the nearest valid sample along x (``x_coords``, or the column index), rows with fewer than two
     valid samples are left alone.  ``missing`` is a boolean array: ``np.nonzero(missing)`` is the reference's ``ind_nans``,
@@ -244,13 +244,13 @@ def fill_na_gpu(values, x_coords=None, min_elevation=None):
     a, rewrap = topo._unwrap(values)
     topo._check_2d(a, "fill_na_gpu")
     x = _fill_coords(x_coords, a.shape[1])
-    src = _lib.as_f32(a)
-    out = np.empty_like(src)
-    missing = np.empty(src.shape, dtype=np.uint8)
+    keep, src, shape = topo._source(a)
+    out = np.empty(shape, dtype=np.float32)
+    missing = np.empty(shape, dtype=np.uint8)
     m = np.nan if min_elevation is None else float(min_elevation)
-    _lib.check(_lib.lib().topo_amd_fill_na_f32(_lib.ptr(src), src.shape[0], src.shape[1],
+    _lib.check(_lib.lib().topo_amd_fill_na_raw(src, shape[0], shape[1],
                                                None if x is None else x.ctypes.data_as(_lib._f64p), m, _lib.ptr(out),
-                                               _lib.ptr(missing)), "topo_amd_fill_na_f32")
+                                               _lib.ptr(missing)), "topo_amd_fill_na_raw")
     return missing.view(np.bool_), rewrap(out)
 
 

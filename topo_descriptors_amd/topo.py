@@ -29,8 +29,8 @@ def __getattr__(name):
 
 # ---- small utilities ------------------------------------------------------------------------
 def _unwrap(dem):
-    """ndarray view of an ndarray or DataArray-like input, plus a re-wrapper."""
-    if isinstance(dem, np.ndarray):
+    """ndarray view of an ndarray or DataArray-like input (a ``PackedDem`` stays what it is), plus a re-wrapper."""
+    if isinstance(dem, (np.ndarray, _lib.PackedDem)):
         return dem, lambda out: out
     if hasattr(dem, "values") and hasattr(dem, "copy"):
         def rewrap(out, src=dem):
@@ -38,8 +38,23 @@ def _unwrap(dem):
                 return src.copy(data=out)
             except TypeError:
                 return out
-        return np.asarray(dem.values), rewrap
+        return _values(dem.values), rewrap
     return np.asarray(dem), lambda out: out
+
+
+def _values(v):
+    return v if isinstance(v, _lib.PackedDem) else np.asarray(v)
+
+
+def _source(values):
+    """``(keep, by-reference Raster, shape)`` of an ndarray or ``PackedDem`` for the ``*_raw`` entry points: supported dtypes
+    go to the GPU as stored (``_lib.as_source``); ``keep`` holds the memory the struct points into."""
+    keep, raster = _lib.source_of(values)
+    return keep, C.byref(raster), keep.shape
+
+
+def _plane(shape):
+    return np.empty(shape, dtype=np.float32)
 
 
 def _check_2d(a, who):
@@ -82,11 +97,11 @@ def tpi(dem, size, sigma=None):
     twice the time on such a DEM."""
     values, rewrap = _unwrap(dem)
     _check_2d(values, "tpi")
-    src = _lib.as_f32(values)
-    out = np.empty_like(src)
+    keep, src, shape = _source(values)
+    out = _plane(shape)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_tpi_f32(_lib.ptr(src), src.shape[0], src.shape[1], int(size),
-                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_tpi_f32")
+    _lib.check(lib.topo_amd_tpi_raw(src, shape[0], shape[1], int(size),
+                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_tpi_raw")
     return rewrap(out)
 
 
@@ -96,11 +111,11 @@ def std(dem, size, sigma=None):
     :func:`tpi` (and :func:`dem` when ``sigma`` is given)."""
     values, _ = _unwrap(dem)
     _check_2d(values, "std")
-    src = _lib.as_f32(values)
-    out = np.empty_like(src)
+    keep, src, shape = _source(values)
+    out = _plane(shape)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_std_f32(_lib.ptr(src), src.shape[0], src.shape[1], int(size),
-                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_std_f32")
+    _lib.check(lib.topo_amd_std_raw(src, shape[0], shape[1], int(size),
+                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_std_raw")
     return out.astype(np.float64)
 
 
@@ -109,13 +124,13 @@ def tpi_std(dem, size, sigma=None):
     the reference convolves three times for the pair)."""
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std")
-    src = _lib.as_f32(values)
-    t = np.empty_like(src)
-    s = np.empty_like(src)
+    keep, src, shape = _source(values)
+    t = _plane(shape)
+    s = _plane(shape)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_tpi_std_f32(_lib.ptr(src), src.shape[0], src.shape[1], int(size),
+    _lib.check(lib.topo_amd_tpi_std_raw(src, shape[0], shape[1], int(size),
                                         _sigma_arg(sigma), _lib.ptr(t), _lib.ptr(s)),
-               "topo_amd_tpi_std_f32")
+               "topo_amd_tpi_std_raw")
     return t, s.astype(np.float64)
 
 
@@ -127,7 +142,7 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
     import ctypes as C
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std_multi")
-    src = _lib.as_f32(values)
+    keep, src, shape = _source(values)
     sizes = np.ascontiguousarray(np.atleast_1d(sizes), dtype=np.int32)
     n = int(sizes.size)
     if sigmas is None:
@@ -135,8 +150,8 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
     else:
         sig = np.array([_sigma_arg(v) for v in np.broadcast_to(np.asarray(sigmas, dtype=object), (n,))],
                        dtype=np.float64)
-    tpis = [np.empty_like(src) for _ in range(n)] if want_tpi else None
-    stds = [np.empty_like(src) for _ in range(n)] if want_std else None
+    tpis = [_plane(shape) for _ in range(n)] if want_tpi else None
+    stds = [_plane(shape) for _ in range(n)] if want_std else None
 
     def plane_list(planes):
         if planes is None:
@@ -145,10 +160,10 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
 
     lib = _lib.lib()
     t_arg, s_arg = plane_list(tpis), plane_list(stds)
-    _lib.check(lib.topo_amd_tpi_std_multi_f32(_lib.ptr(src), src.shape[0], src.shape[1], n,
+    _lib.check(lib.topo_amd_tpi_std_multi_raw(src, shape[0], shape[1], n,
                                               sizes.ctypes.data_as(C.POINTER(C.c_int32)),
                                               sig.ctypes.data_as(C.POINTER(C.c_double)), t_arg, s_arg),
-               "topo_amd_tpi_std_multi_f32")
+               "topo_amd_tpi_std_multi_raw")
     return tpis, ([s.astype(np.float64) for s in stds] if stds is not None else None)
 
 
@@ -170,11 +185,11 @@ def dem(dem, sigma):
     values, rewrap = _unwrap(dem)
     _check_2d(values, "dem")
     sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (2,))
-    src = _lib.as_f32(values)
-    out = np.empty_like(src)
+    keep, src, shape = _source(values)
+    out = _plane(shape)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_gauss_f32(_lib.ptr(src), src.shape[0], src.shape[1], float(sig[0]),
-                                      float(sig[1]), _lib.ptr(out)), "topo_amd_gauss_f32")
+    _lib.check(lib.topo_amd_gauss_raw(src, shape[0], shape[1], float(sig[0]),
+                                      float(sig[1]), _lib.ptr(out)), "topo_amd_gauss_raw")
     return rewrap(out)
 
 
@@ -182,12 +197,12 @@ def sobel(dem):
     """Sobel derivative pair (dx, dy), kernel / 8, reflect boundary (reference topo.py:658-685)."""
     values, _ = _unwrap(dem)
     _check_2d(values, "sobel")
-    src = _lib.as_f32(values)
-    dx = np.empty_like(src)
-    dy = np.empty_like(src)
+    keep, src, shape = _source(values)
+    dx = _plane(shape)
+    dy = _plane(shape)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_sobel_f32(_lib.ptr(src), src.shape[0], src.shape[1], _lib.ptr(dx),
-                                      _lib.ptr(dy)), "topo_amd_sobel_f32")
+    _lib.check(lib.topo_amd_sobel_raw(src, shape[0], shape[1], _lib.ptr(dx),
+                                      _lib.ptr(dy)), "topo_amd_sobel_raw")
     return dx, dy
 
 
@@ -220,13 +235,13 @@ def gradient(dem, sigma, res_meters, sig_ratio=1):
     :func:`dem` (plus the one pixel of the finite difference)."""
     values, _ = _unwrap(dem)
     _check_2d(values, "gradient")
-    src = _lib.as_f32(values)
-    mode, rx, ry = _resolution_args(res_meters, src.shape)
-    outs = [np.empty_like(src) for _ in range(4)]
+    keep, src, shape = _source(values)
+    mode, rx, ry = _resolution_args(res_meters, shape)
+    outs = [_plane(shape) for _ in range(4)]
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_gradient_f32(_lib.ptr(src), src.shape[0], src.shape[1], float(sigma),
+    _lib.check(lib.topo_amd_gradient_raw(src, shape[0], shape[1], float(sigma),
                                          float(sig_ratio), mode, _lib.ptr(rx), _lib.ptr(ry),
-                                         *[_lib.ptr(o) for o in outs]), "topo_amd_gradient_f32")
+                                         *[_lib.ptr(o) for o in outs]), "topo_amd_gradient_raw")
     return outs
 
 
@@ -275,14 +290,13 @@ def _sx_scan(dem, reach, rows, cols, metres, height):
     """Kernel K6 on a host array: for every pixel the largest elevation angle (degrees) towards the ray pixels
     ``(rows[k], cols[k])`` (offsets from the pixel) at ``metres[k]`` horizontal distance, seen from ``height``
     above the pixel.  NaN distances are skipped; a frame of ``reach`` pixels stays 0."""
-    dem = np.asarray(dem)
+    dem = _values(dem)
     _check_2d(dem, "_sx_rolling")
     metres = np.ascontiguousarray(metres, dtype=np.float64)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
-    src = _lib.as_f32(dem)
-    out = np.zeros_like(src)
-    ny, nx = src.shape
+    keep, src, (ny, nx) = _source(dem)
+    out = np.zeros((ny, nx), dtype=np.float32)
     if ny <= 2 * reach or nx <= 2 * reach:  # nothing but frame
         return out.astype(dem.dtype, copy=False)
     if metres.size == 0 or np.all(np.isnan(metres)):
@@ -290,10 +304,10 @@ def _sx_scan(dem, reach, rows, cols, metres, height):
         out[reach : ny - reach, reach : nx - reach] = np.nan
         return out.astype(dem.dtype, copy=False)
     lib = _lib.lib()
-    _lib.check(lib.topo_amd_sx_f32(_lib.ptr(src), ny, nx, rows.ctypes.data_as(_lib._i32p),
+    _lib.check(lib.topo_amd_sx_raw(src, ny, nx, rows.ctypes.data_as(_lib._i32p),
                                    cols.ctypes.data_as(_lib._i32p), metres.ctypes.data_as(_lib._f64p),
                                    int(metres.size), int(reach), float(height), _lib.ptr(out)),
-               "topo_amd_sx_f32")
+               "topo_amd_sx_raw")
     return out.astype(dem.dtype, copy=False)
 
 
@@ -350,11 +364,10 @@ def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_st
     dx = res_meters["x"].mean()
     dy = res_meters["y"].mean()
     sectors = [device.sx_offsets(a, radius, dx, dy, azimuth_arc, azimuth_steps, radius_min) for a in azimuths]
-    dem = np.asarray(hlp.get_da(dem_ds).values)
+    dem = _values(hlp.get_da(dem_ds).values)
     _check_2d(dem, "sx_multi")
-    src = _lib.as_f32(dem)
-    ny, nx = src.shape
-    outs = [np.zeros_like(src) for _ in sectors]
+    keep, src, (ny, nx) = _source(dem)
+    outs = [np.zeros((ny, nx), dtype=np.float32) for _ in sectors]
     # sectors the device has something to do for: the DEM is larger than the zero frame and there
     # is a usable ray pixel (else zeros, or NaN inside the frame, as in _sx_rolling)
     todo = []
@@ -368,10 +381,10 @@ def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_st
     if todo:
         first, dj, di, dist, window = device.pack_sectors([sectors[k] for k in todo])
         planes = (C.c_void_p * len(todo))(*[_lib.ptr(outs[k]) for k in todo])
-        _lib.check(_lib.lib().topo_amd_sx_multi_f32(
-            _lib.ptr(src), ny, nx, len(todo), first.ctypes.data_as(_lib._i32p), dj.ctypes.data_as(_lib._i32p),
+        _lib.check(_lib.lib().topo_amd_sx_multi_raw(
+            src, ny, nx, len(todo), first.ctypes.data_as(_lib._i32p), dj.ctypes.data_as(_lib._i32p),
             di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
-            float(height), planes), "topo_amd_sx_multi_f32")
+            float(height), planes), "topo_amd_sx_multi_raw")
     return [o.astype(dem.dtype, copy=False) for o in outs]
 
 
@@ -470,15 +483,17 @@ def valley_ridge(dem, size, mode, flat_list=[0, 0.15, 0.3], sigma=None):  # noqa
     values, _ = _unwrap(dem)
     _check_2d(values, "valley_ridge")
     field = globals()["dem"](values, sigma) if sigma else values
-    src = _lib.as_f32(field)
-    # the reference standardises with numpy's own float32 mean / std of the whole array (topo.py:427)
-    mean, stdev = float(field.mean()), float(field.std())
+    keep, src, shape = _source(field)
+    # the reference standardises with numpy's own float32 mean / std of the whole array (topo.py:427); a PackedDem is the
+    # float32 array it decodes to
+    host = field.decode() if isinstance(field, _lib.PackedDem) else field
+    mean, stdev = float(host.mean()), float(host.std())
     kernels = _ridge_kernels(size, flat_list) if mode == "ridge" else _valley_kernels(size, flat_list)
     taps, ksize, angles = _valley_ridge_tables(kernels, np.arange(0, 180, dtype=np.float32))
-    norm = np.empty(src.shape, dtype=np.float32)
-    direction = np.empty(src.shape, dtype=np.float32)
-    _lib.check(_lib.lib().topo_amd_valley_ridge_f32(
-        src.ctypes.data_as(_lib._vp), src.shape[0], src.shape[1], taps.ctypes.data_as(_lib._vp),
+    norm = _plane(shape)
+    direction = _plane(shape)
+    _lib.check(_lib.lib().topo_amd_valley_ridge_raw(
+        src, shape[0], shape[1], taps.ctypes.data_as(_lib._vp),
         ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size, kernels.shape[0], mean, stdev,
-        norm.ctypes.data_as(_lib._vp), direction.ctypes.data_as(_lib._vp)), "topo_amd_valley_ridge_f32")
+        norm.ctypes.data_as(_lib._vp), direction.ctypes.data_as(_lib._vp)), "topo_amd_valley_ridge_raw")
     return [norm, direction]
