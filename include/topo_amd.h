@@ -223,7 +223,11 @@ int topo_amd_gradient_dev(const float* in, int in_rows, int in_row0, int gny, in
 /* Sx max-elevation-angle scan (replaces topo._sx_rolling topo.py:928-953, called from :856).
  * dj/di: offsets of the ray pixels relative to the target (host int32, n_off entries,
  * duplicates allowed); dist: metric distance of each (host double, NaN = skip, as left by
- * radius_min at topo.py:845); window: zero-frame width int(W/2); height: topo.py:947.     */
+ * radius_min at topo.py:845); window: zero-frame width int(W/2); height: topo.py:947.
+ * Non-finite samples as in numpy's nanmax over the angles: a NaN ray sample is skipped, whether
+ * quiet or signalling; a pixel whose own sample is NaN, or whose ray samples are all NaN, is
+ * NaN; +inf on a ray gives 90, and a pixel whose own sample is +inf (or whose ray samples are
+ * all -inf) gives -90.                                                                     */
 int topo_amd_sx_dev(const float* in, int in_rows, int in_row0, int gny, int nx,
                     const int32_t* dj, const int32_t* di, const double* dist, int n_off,
                     int window, double height, int out_row0, int out_rows, float* out);
@@ -286,6 +290,17 @@ int topo_amd_valley_route(int* route);
  * its whole-metre tiles with (for tests and diagnostics): 1 the wide ring (TPI alone, 67 px, a single block of a
  * whole-metre raster class: csrc/disc_ring_wide_impl.hpp), 0 any other kernel.                                        */
 int topo_amd_tpi_route(int* route);
+/* Which kernel route the calling thread's last Sx call took (topo_amd_sx_dev, topo_amd_sx_multi_dev and the calls built on
+ * them; for tests and diagnostics).  Bits 0 - 2, the scan: 0 chains down the columns, 1 along the rows, 2 along the diagonal
+ * (dj + 1, di + 1), 3 along the diagonal (dj + 1, di - 1), 4 the kernel without an LDS tile (sx_global_kernel: a search window
+ * too large for LDS; every other bit is 0 then).  + 8: tiles of 64 x 128 pixels with 8 waves (else 64 x 64 with 4).  The chain
+ * tables that held at least one chain: + 16 eights, + 32 fours, + 64 twos, + 128 pairs of eights, + 256 pairs of fours, + 512
+ * pairs of twos.  Bits 10 - 13: the index of the LDS row stride among the 16 the kernels are built for (67, 71, 75, 81, 89,
+ * 97, 105, 113, 129, 145, 161, 177, 193, 209, 225, 257).  + 16384: topo_amd_sx_multi_dev ran at least one group of more than
+ * one sector in a single launch of the multi-sector kernel; the other bits are those of the call's last launch (a grouped
+ * launch scans down the columns or along the rows, with 4 waves and without pairs).  -1: no usable ray pixel, nothing
+ * scanned.                                                                                                               */
+int topo_amd_sx_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);

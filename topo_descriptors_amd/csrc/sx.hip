@@ -73,6 +73,19 @@ struct SxArgs {
 constexpr int kSxTile = 64;                     // output tile: 64 x 64 pixels
 constexpr int kSxOwn = kSxTile / (kThreads / 64);  // consecutive pixels per lane along the chain axis
 
+// Non-finite samples.  A NaN sample makes its products NaN and max3 drops them; the maximum starts as NaN, so a pixel without
+// a usable product (every ray sample NaN, or its own sample NaN) stays NaN, and one whose products are all -inf (its own
+// sample +inf, or every ray sample -inf) gets atan(-inf) = -90 like numpy's nanmax.  The pairs compare raw SAMPLES: v_max_f32
+// returns the other operand for a quiet NaN but, in IEEE mode, the quieted NaN for a SIGNALLING one - the other sample of
+// the pair would be lost - so the samples are quieted on their way into LDS (the subtraction does it for the products):
+// times 1.0, a full-rate v_mul_f32 spelled out because the compiler's canonicalize is the half-rate v_max_f32 v, v, v.
+// Timings of both against the kernel without: profiles/sx_nonfinite_ab.txt.
+__device__ __forceinline__ float quiet(float v) {
+    float r;
+    asm("v_mul_f32 %0, 1.0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
+
 // A lane owns kSxOwn consecutive pixels along the chain axis (ALONG_X false: 16 rows of one column, lanes along x;
 // true: 16 columns of one row, lanes along y).  The ray pixels of a sector are dense in (dj, di): along the axis
 // the sector points in they come in long runs of neighbours, and the sample a lane needs for (own pixel k, ray
@@ -145,7 +158,7 @@ __global__ __launch_bounds__(NW * 64) void sx_kernel(SxArgs p) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int r = r0 + wave + NW * u;
-                        if (r < p.rows_l) L[r * STRIDE + k] = v[u];
+                        if (r < p.rows_l) L[r * STRIDE + k] = quiet(v[u]);
                     }
                 }
             }
@@ -167,7 +180,7 @@ __global__ __launch_bounds__(NW * 64) void sx_kernel(SxArgs p) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int r = r0 + wave + NW * u;
-                        if (r < p.rows_l) L[r * STRIDE + k] = v[u];
+                        if (r < p.rows_l) L[r * STRIDE + k] = quiet(v[u]);
                     }
                 }
             }
@@ -182,7 +195,7 @@ __global__ __launch_bounds__(NW * 64) void sx_kernel(SxArgs p) {
     const int self = -p.dj_min * STRIDE - p.di_min;
 #pragma unroll
     for (int k = 0; k < kSxOwn; ++k) {
-        best[k] = -INFINITY;
+        best[k] = NAN;
         centre[k] = Lw[self + k * S] + p.height;
     }
     for (int c = 0; c < p.n8; ++c) {
@@ -244,8 +257,9 @@ __global__ __launch_bounds__(NW * 64) void sx_kernel(SxArgs p) {
     // Pairs (round 3).  A sector that points along an axis is symmetric about it: the ray pixels (dj, di) and (dj, -di)
     // are equally far, so their chains carry the same weights, and since (w - c) inv grows with w the larger of the two
     // SAMPLES decides - one v_max per sample (8 + 15 of them) instead of a second set of 8 x 16 products and their
-    // maxima.  The launcher pairs any two chains of one length whose weights are equal bit for bit.  NaN: v_max
-    // returns the other operand, as the two separate products would have been dropped one by one.
+    // maxima.  The launcher pairs any two chains of one length whose weights are equal bit for bit.  A quiet NaN: v_max
+    // returns the other operand, as the two separate products would have been dropped one by one (the samples in LDS are
+    // quiet: see quiet() above).
     auto larger = [](float a, float b) {
         float m;
         asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
@@ -318,7 +332,7 @@ __global__ __launch_bounds__(NW * 64) void sx_kernel(SxArgs p) {
         const bool inside = oy >= p.window && oy < p.gny - p.window && ox >= p.window &&
                             ox < p.nx - p.window;
         float v = 0.0f;
-        if (inside) v = best[k] == -INFINITY ? NAN : atan_signed(best[k]) * rad2deg;
+        if (inside) v = atan_signed(best[k]) * rad2deg;
         p.out[(size_t)(oy - p.out_row0) * p.nx + ox] = v;
     }
 }
@@ -365,6 +379,17 @@ int sx_stride_for(int cols_l) {
     for (int s : kSxStrides)
         if (s >= cols_l) return s;
     return 0;
+}
+
+// The code topo_amd_sx_route reports (include/topo_amd.h): scan 0 ... 3 (4: sx_global_kernel), + 8 for 8 waves, + 16 ... 512
+// for the tables that hold a chain (8 / 4 / 2 singles, 8 / 4 / 2 pairs), the index of the LDS stride in kSxStrides from
+// bit 10, + 16384 for a grouped launch of sx_multi_kernel.
+constexpr int kSxRouteGlobal = 4, kSxRouteWaves8 = 8, kSxRouteGrouped = 1 << 14;
+int sx_route_code(int scan, int waves, size_t n8, size_t n4, size_t n2, size_t n8p, size_t n4p, size_t n2p, int stride) {
+    int index = 0;
+    while (index < kSxStrideCount && kSxStrides[index] != stride) ++index;
+    return scan + (waves == 8 ? kSxRouteWaves8 : 0) + (n8 ? 16 : 0) + (n4 ? 32 : 0) + (n2 ? 64 : 0) + (n8p ? 128 : 0) +
+           (n4p ? 256 : 0) + (n2p ? 512 : 0) + (index << 10);
 }
 
 // Cut the unique ray pixels into chains along one axis: runs of neighbours in eights, what is left of a run (or
@@ -513,12 +538,12 @@ __global__ __launch_bounds__(kThreads) void sx_multi_kernel(SxMultiArgs p) {
     for (int k = 0; k < OWN; ++k) {
         centre[k] = Lw[self + k * S] + p.height;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) best[a][k] = -INFINITY;
+        for (int a = 0; a < NA; ++a) best[a][k] = NAN;
     }
     for (int c = 0; c < p.n_cls; ++c) {
         float top[OWN];
 #pragma unroll
-        for (int k = 0; k < OWN; ++k) top[k] = -INFINITY;
+        for (int k = 0; k < OWN; ++k) top[k] = NAN;
         const int e8 = p.cls_first8[c + 1], e4 = p.cls_first4[c + 1], e2 = p.cls_first2[c + 1];
         for (int n = p.cls_first8[c]; n < e8; ++n) {
             const SxChain8 e = p.tab8[n];
@@ -601,7 +626,7 @@ __global__ __launch_bounds__(kThreads) void sx_multi_kernel(SxMultiArgs p) {
                 if (ox >= p.nx || oy >= p.out_row0 + p.out_rows) continue;
                 const bool inside = oy >= w && oy < p.gny - w && ox >= w && ox < p.nx - w;
                 float v = 0.0f;
-                if (inside) v = t == -INFINITY ? NAN : atan_signed(t) * rad2deg;
+                if (inside) v = atan_signed(t) * rad2deg;
                 p.out[a][(size_t)(oy - p.out_row0) * p.nx + ox] = v;
             }
         } else {
@@ -613,7 +638,7 @@ __global__ __launch_bounds__(kThreads) void sx_multi_kernel(SxMultiArgs p) {
                     if (oy >= p.out_row0 + p.out_rows) continue;
                     const bool inside = oy >= w && oy < p.gny - w && ox >= w && ox < p.nx - w;
                     float v = 0.0f;
-                    if (inside) v = best[a][k] == -INFINITY ? NAN : atan_signed(best[a][k]) * rad2deg;
+                    if (inside) v = atan_signed(best[a][k]) * rad2deg;
                     p.out[a][(size_t)(oy - p.out_row0) * p.nx + ox] = v;
                 }
             }
@@ -646,12 +671,12 @@ __global__ __launch_bounds__(kThreads) void sx_global_kernel(SxGlobalArgs p) {
         return;
     }
     const float centre = p.in[(size_t)(oy - p.in_row0) * p.nx + ox] + p.height;
-    float best = -INFINITY;
+    float best = NAN;
     for (int n = 0; n < p.n_off; ++n) {
         const float v = p.in[(size_t)(oy + p.dj[n] - p.in_row0) * p.nx + ox + p.di[n]];
         best = fmaxf(best, (v - centre) * p.inv_dist[n]);
     }
-    p.out[o] = best == -INFINITY ? NAN : atan_signed(best) * 57.29577951308232f;
+    p.out[o] = atan_signed(best) * 57.29577951308232f;
 }
 
 __global__ __launch_bounds__(kThreads) void fill_kernel(float* out, size_t n, float value) {
@@ -699,8 +724,11 @@ int launch_synth(float* out, int rows, int row0, int nx, uint32_t seed, bool int
     return TOPO_AMD_OK;
 }
 
-int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double* dist, int n_off,
-              int window, double height, float* out) {
+namespace {
+
+// launch_sx; *route: the code of the scan that was launched (-1: no usable ray pixel), untouched when none was
+int sx_single(const Block& b, const int32_t* dj, const int32_t* di, const double* dist, int n_off,
+              int window, double height, float* out, int* route) {
     Context& c = ctx();
     TOPO_REQUIRE(window >= 0, "sx: negative window %d", window);
     // unique (dj, di) with a finite, usable distance
@@ -725,6 +753,7 @@ int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double
         hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(kThreads), 0, c.compute, out, total, 0.0f);
         TOPO_HIP(hipGetLastError());
         set_error("sx: no usable ray pixel (all distances NaN)");
+        *route = -1;
         return TOPO_AMD_EEMPTY;
     }
     SxArgs a;
@@ -761,6 +790,7 @@ int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double
         dim3 ggrid((b.nx + kThreads - 1) / kThreads, b.out_rows);
         hipLaunchKernelGGL(sx_global_kernel, ggrid, dim3(kThreads), 0, c.compute, ga);
         TOPO_HIP(hipGetLastError());
+        *route = kSxRouteGlobal;
         return TOPO_AMD_OK;
     }
     // chains along the direction that needs the fewest comparisons (padding included): down the columns, along the
@@ -904,7 +934,9 @@ int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double
     if (diag != 0) {
         a.cols_l = cols_d;
         dim3 dgrid((b.nx + kSxTile - 1) / kSxTile + 1, (b.out_rows + kSxTile - 1) / kSxTile);  // the slabs lean: one tile more
-        return go(stride_d, false, 4, dgrid, lds_d, diag, kSxTile);
+        TOPO_TRY(go(stride_d, false, 4, dgrid, lds_d, diag, kSxTile));
+        *route = sx_route_code(mode, 4, a.n8, a.n4, a.n2, a.n8p, a.n4p, a.n2p, stride_d);
+        return TOPO_AMD_OK;
     }
     if (!along_x && b.out_rows >= 2 * kSxTile && scan_cost >= 256) {
         const size_t lds8 = (size_t)(a.rows_l + kSxTile + 8) * stride * sizeof(float);
@@ -916,7 +948,19 @@ int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double
     }
     const int span = kSxOwn * waves;
     dim3 grid((b.nx + kSxTile - 1) / kSxTile, (b.out_rows + span - 1) / span);
-    return go(stride, along_x, waves, grid, lds_used, 0, along_x ? kSxTile : span);
+    TOPO_TRY(go(stride, along_x, waves, grid, lds_used, 0, along_x ? kSxTile : span));
+    *route = sx_route_code(mode, waves, a.n8, a.n4, a.n2, a.n8p, a.n4p, a.n2p, stride);
+    return TOPO_AMD_OK;
+}
+
+}  // namespace
+
+int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double* dist, int n_off,
+              int window, double height, float* out) {
+    int route = 0;
+    const int rc = sx_single(b, dj, di, dist, n_off, window, height, out, &route);
+    if (rc == TOPO_AMD_OK || rc == TOPO_AMD_EEMPTY) note_sx_route(route);
+    return rc;
 }
 
 namespace {
@@ -967,7 +1011,7 @@ size_t sx_tile_bytes(int dj_min, int dj_max, int di_min, int di_max) {
 
 // one launch of sx_multi_kernel for sectors [a0, a1)
 int launch_sx_group(const Block& b, const std::vector<SectorPoints>& sec, int a0, int a1,
-                    const int32_t* window, double height, float* const* outs) {
+                    const int32_t* window, double height, float* const* outs, int* route) {
     Context& c = ctx();
     std::vector<std::pair<std::pair<int, int>, std::pair<int, double>>> all;  // (dj, di) -> (mask, dist)
     SxMultiArgs a;
@@ -1081,7 +1125,10 @@ int launch_sx_group(const Block& b, const std::vector<SectorPoints>& sec, int a0
     a.out_rows = b.out_rows;
     a.height = (float)height;
     dim3 grid((b.nx + tw - 1) / tw, (b.out_rows + th - 1) / th);
-    return launch_sx_multi_stride(stride, along_x, grid, lds, c.compute, a);
+    // (sx_multi_kernel: chains down the columns or along the rows, 4 waves, no pairs; the counts are those of all classes)
+    TOPO_TRY(launch_sx_multi_stride(stride, along_x, grid, lds, c.compute, a));
+    *route = sx_route_code(along_x ? 1 : 0, 4, first8.back(), first4.back(), first2.back(), 0, 0, 0, stride);
+    return TOPO_AMD_OK;
 }
 
 }  // namespace
@@ -1113,6 +1160,8 @@ int launch_sx_multi(const Block& b, int n_az, const int32_t* first, const int32_
         }
     }
     int rc = TOPO_AMD_OK;
+    int route = 0;  // the route of the call: that of its last launch, + "grouped" if any of its launches was
+    bool grouped = false, launched = false;
     for (int a0 = 0; a0 < n_az;) {
         // neighbouring sectors while their common tile stays small; a sector on its own (or one
         // without a usable ray pixel) takes the single-azimuth path, whatever its size
@@ -1127,13 +1176,16 @@ int launch_sx_multi(const Block& b, int n_az, const int32_t* first, const int32_
         }
         if (a1 - a0 == 1) {
             const int n0 = first[a0];
-            const int r = launch_sx(b, dj + n0, di + n0, dist + n0, first[a0 + 1] - n0, window[a0], height, outs[a0]);
+            const int r = sx_single(b, dj + n0, di + n0, dist + n0, first[a0 + 1] - n0, window[a0], height, outs[a0], &route);
             if (r != TOPO_AMD_OK) rc = r;  // an empty sector: reported at the end, the others still run
+            launched = launched || r == TOPO_AMD_OK || r == TOPO_AMD_EEMPTY;
         } else {
-            TOPO_TRY(launch_sx_group(b, sec, a0, a1, window, height, outs));
+            TOPO_TRY(launch_sx_group(b, sec, a0, a1, window, height, outs, &route));
+            grouped = launched = true;
         }
         a0 = a1;
     }
+    if (launched) note_sx_route(grouped && route >= 0 ? route | kSxRouteGrouped : route);
     return rc;
 }
 

@@ -148,6 +148,17 @@ def valley_route():
     return n.value
 
 
+def sx_route():
+    """The kernel route the calling thread's last Sx call took (``topo_amd_sx_route``): bits 0 - 2 the scan (0 chains down the
+    columns, 1 along the rows, 2 / 3 along the diagonals (dj + 1, di + 1) / (dj + 1, di - 1), 4 the kernel without an LDS tile);
+    + 8 with 8 waves; + 16 / 32 / 64 chains of 8 / 4 / 2, + 128 / 256 / 512 pairs of them; bits 10 - 13 the index of the LDS
+    stride among the 16 the kernels are built for (``include/topo_amd.h``); + 16384 when ``sx_multi`` ran a group of several sectors in one launch (the other bits: the
+    call's last launch); -1 without a usable ray pixel."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().topo_amd_sx_route(C.byref(n)), "sx_route")
+    return n.value
+
+
 def dem_changed(array):
     """Tell the library that ``array`` (a :class:`DeviceArray`) was written by something other than the library."""
     _lib.check(_lib.lib().topo_amd_dem_changed(array.ptr, array.nbytes), "dem_changed")
