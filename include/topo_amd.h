@@ -301,6 +301,28 @@ int topo_amd_tpi_route(int* route);
  * launch scans down the columns or along the rows, with 4 waves and without pairs).  -1: no usable ray pixel, nothing
  * scanned.                                                                                                               */
 int topo_amd_sx_route(int* route);
+/* Which kernels the calling thread's last gradient call queued (topo_amd_gradient_dev and the calls built on it; for tests
+ * and diagnostics): what the host decided, noted once every launch of the call succeeded.  A call taller than one launch
+ * covers reports its last part.
+ *   bits 0 - 2   the route: 0 Sobel (sigma <= 1; every other field is 0), 1 Chunked (matrix cores, row chunks with the
+ *                epilogue of one next to the smooth of the next), 2 Mfma (matrix cores, one shot), 3 Valu (vector-ALU
+ *                kernels), 4 Aniso (sig_ratio != 1: two smooths).
+ *   bits 3 - 5   the smooth: 0 none, 1 the fused f16 kernel with the two passes queued behind its flag, 2 the two-pass tile
+ *                kernels, 3 two passes with the split-once axis 1, 4 vector-ALU axis 0 (Aniso: vector-ALU passes only;
+ *                otherwise the highest of 2 / 3 among its four passes).
+ *   bit 6        Aniso: some of its passes ran on the vector ALUs, some on the matrix cores.
+ *   bits 7 - 11  the step count of that f16 kernel: 4 / 6 / 8 of the fused kernel, 4 ... 18 of the tile kernels, NK 5 / 7 / 9 of
+ *                the split-once axis 1 (0 without matrix-core pass).
+ *   bits 12 - 13 the axis-1 finish of the Valu route: 0 none, 1 LDS-tiled axis 1 + epilogue, 2 wave-shift axis 1 +
+ *                epilogue, 3 unfused (axis 1 alone, then a stand-alone epilogue).
+ *   bit 14       LDS-tiled finish: tap chunks of 16 (KB 16; else 8).    bits 15 - 17: its PF (3, 4 or 5 samples per lane
+ *                held for the next tile; 0 without that kernel).
+ *   bits 18 - 19 the stand-alone epilogue: 0 none, 1 one pixel a thread (rows under 8 columns), 2 four pixels a thread.
+ *   bit 20       an _if epilogue was queued behind a deferred two-pass smooth (it runs only if the fused kernels of the
+ *                chunks met a sample that is not a plain finite one).
+ *   bit 21       the row chunks were tapered (first and last a quarter of the others).
+ *   bits 22 - 28 the number of row chunks (0 unless Chunked).                                                             */
+int topo_amd_gradient_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);

@@ -80,8 +80,10 @@ def test_tpi_std_blocks_bit_identical(size, nx, integer):
     assert np.max(np.abs(whole[1] - e)) <= 1e-4 * np.max(e)
 
 
-# radius int(4 sigma + 0.5): 13, 28 and 48 (fused LDS-tiled axis 1, 3 / 3 / 4 samples per lane held for
-# the next tile), 64 and 88 (the same kernel with 16-wide tap chunks, 4 / 5 samples), 104 (wave-shift axis 1)
+# radius int(4 sigma + 0.5): 3 (Sobel), 13, 28 and 40 (the fused f16 matrix-core kernel with 4 / 6 / 8 steps, the two passes
+# queued behind its flag), 48 (the two-pass f16 tile kernels), 64, 88 and 104 (two passes with the split-once axis 1, NK
+# 5 / 7 / 9), each followed by the stand-alone epilogue, four pixels a thread.  (The vector-ALU kernels with the epilogue
+# fused in, which this test ran before the matrix-core floor dropped to radius 4: tests/test_gpu_gradient_routes.py.)
 @pytest.mark.parametrize("sigma", [0.75, 3.25, 7.0, 10.0, 12.0, 16.0, 22.0, 26.0])
 def test_gradient_blocks_bit_identical(sigma):
     gny, nx = 420, 320

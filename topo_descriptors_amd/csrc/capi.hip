@@ -532,6 +532,7 @@ int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float*
 thread_local int t_tpi_route = 0;     // 1: the calling thread's last TPI / STD disc call took the wide ring (topo_amd_tpi_route)
 thread_local int t_valley_route = 0;  // the evaluation the calling thread's last valley / ridge call took (topo_amd_valley_route)
 thread_local int t_sx_route = 0;      // the kernel route the calling thread's last Sx call took (topo_amd_sx_route)
+thread_local int t_gradient_route = 0;  // the same of its last gradient call (topo_amd_gradient_route)
 thread_local int t_host_chunks = 0;  // row chunks of the calling thread's last host-buffer call (topo_amd_host_chunks)
 struct HostRun {
     std::vector<void*> bufs;
@@ -871,6 +872,7 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
 void note_tpi_route(int route) { t_tpi_route = route; }
 void note_valley_route(int route) { t_valley_route = route; }
 void note_sx_route(int route) { t_sx_route = route; }
+void note_gradient_route(int route) { t_gradient_route = route; }
 
 }  // namespace topo
 
@@ -1099,6 +1101,12 @@ int topo_amd_valley_route(int* route) {
 int topo_amd_sx_route(int* route) {
     TOPO_REQUIRE(route != nullptr, "sx_route: NULL output");
     *route = t_sx_route;
+    return TOPO_AMD_OK;
+}
+
+int topo_amd_gradient_route(int* route) {
+    TOPO_REQUIRE(route != nullptr, "gradient_route: NULL output");
+    *route = t_gradient_route;
     return TOPO_AMD_OK;
 }
 

@@ -233,6 +233,7 @@ int valley_ridge_reach(const int32_t* ksize, int n_angles, int* above, int* belo
 void note_tpi_route(int route);     // what topo_amd_tpi_route reports for the calling thread (capi.hip)
 void note_valley_route(int route);  // what topo_amd_valley_route reports for the calling thread (capi.hip)
 void note_sx_route(int route);      // what topo_amd_sx_route reports for the calling thread (capi.hip)
+void note_gradient_route(int route);  // what topo_amd_gradient_route reports for the calling thread (capi.hip)
 // the same on the matrix pipe for rotated kernels of up to kValleyMfmaMaxKernel cells a side with at most 240 cells that hold a
 // tap at any angle (valley_mfma.hip; *done = 0: not such a case, nothing launched); leaves the pixels it cannot do marked
 // norm = g.mark and their tiles (kValleyMfmaTileRows x 64, anchored at out_row0) flagged.  n_planes (1..4): planes g.p0 ...

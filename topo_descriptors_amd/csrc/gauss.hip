@@ -199,17 +199,20 @@ struct GradArgs {
 // accuracy (atan: Abramowitz & Stegun 4.4.49, |err| <= 2e-8 on [0,1]; division: reciprocal plus
 // one FMA correction, correctly rounded except in rare half-way cases) and the IEEE special cases
 // the descriptors rely on: signed zeros (flat terrain: dy = -0 -> atan2(+0,-0) = pi -> aspect 0),
-// NaN propagation, slope 90 for infinite gradients.
+// NaN propagation, and numpy's values for infinite gradients: dx, dy +-inf, slope 90 (np.hypot: an infinite component wins
+// over a NaN one), aspect atan2's (90 / 270 for an infinite dx, 0 / 180 for an infinite dy, 45 ... 315 for both).
 __device__ __forceinline__ float div_f32(float a, float b) {
     const float r = __builtin_amdgcn_rcpf(b);
     const float q = a * r;
-    return fmaf(fmaf(-q, b, a), r, q);
+    const float c = fmaf(fmaf(-q, b, a), r, q);
+    return fabsf(q) == INFINITY ? q : c;  // (the correction of an infinite quotient is inf - inf)
 }
 
 __device__ __forceinline__ float atan2_f32(float y, float x) {
     const float a = fabsf(y), b = fabsf(x);
     const float mx = fmaxf(a, b), mn = fminf(a, b);
-    const float t = mx == 0.0f ? 0.0f : mn * __builtin_amdgcn_rcpf(mx);
+    // (both infinite: inf * rcp(inf) would be NaN; atan2 says pi / 4)
+    const float t = mx == 0.0f ? 0.0f : (mn == INFINITY ? 1.0f : mn * __builtin_amdgcn_rcpf(mx));
     float r = atan_unit(t);
     if (a > b) r = 1.5707963267948966f - r;
     if (__float_as_uint(x) >> 31) r = 3.14159265358979323846f - r;  // sign BIT: x = -0 counts
@@ -239,7 +242,8 @@ __device__ __forceinline__ void gradient_values(float& dx, float& dy, float rx, 
     const float rad2deg = 57.29577951308232f;
     const float d2 = dx * dx;
     const float e2 = dy * dy;
-    slope = atan_pos(__builtin_amdgcn_sqrtf(d2 + e2)) * rad2deg;
+    const float h = fmaxf(fabsf(dx), fabsf(dy)) == INFINITY ? INFINITY : __builtin_amdgcn_sqrtf(d2 + e2);  // (fmaxf drops a NaN)
+    slope = atan_pos(h) * rad2deg;
     float a = 180.0f + atan2_f32(dx, dy) * rad2deg;
     if (a >= 360.0f) a -= 360.0f;  // float32 "% 360" of a value in [0, 360]
     aspect = a;
@@ -1889,6 +1893,20 @@ int gauss_args(const Block& b, float* out, double sigma, int kb, int slot, Gauss
 // a plane of `rows` rows taken as a raster of its own
 Block plane_block(const float* in, int rows, int nx) { return Block{in, rows, 0, rows, nx, 0, rows}; }
 
+// What topo_amd_gradient_route reports (include/topo_amd.h): the launchers below note what they decide as they go,
+// launch_gradient clears the note first and packs it once its launches succeeded.  (The Gaussian writes it too; nobody reads that.)
+struct GradNote {
+    int fused_steps = 0, tile_steps = 0, s1_steps = 0;  // step counts of the f16 kernels that were queued (0: none)
+    bool valu_smooth = false;                            // a pass on the vector-ALU kernels
+    int finish = 0, kb = 0, pf = 0;                      // axis-1 finish of the Valu route (kGradFinish*), its tap chunk and PF
+    int epilogue = 0;                                    // stand-alone epilogue: 1 one pixel a thread, 2 four
+    bool rerun = false;                                  // an _if epilogue behind a deferred two-pass smooth
+    int chunks = 0;
+    bool taper = false;
+};
+thread_local GradNote t_grad;
+constexpr int kGradFinishTiled = 1, kGradFinishWave = 2, kGradFinishUnfused = 3;
+
 // the cut of each of `lines` lines of `ntile` tiles into at most max(1, max_runs) runs with the least rounds x (tiles per
 // run + the `halo` tiles a run restages), `slots` lines running at once
 int run_cut(long lines, int ntile, int max_runs, long slots, int halo) {
@@ -2080,6 +2098,7 @@ int run_axis0_mfma(const Block& b, double sigma, float* out, int table_slot, con
     TOPO_TRY(gauss_args(b, out, sigma, 1, table_slot, &a));
     set_f16_scales(sigma, &a);
     a.run_if = tp.run_if;
+    t_grad.tile_steps = f16_steps(a.radius);
     const int mt = f16_mt(false, a.radius, tp.one_tile), tile = 32 * mt;
     const int tile_first = b.out_row0 / tile;
     const int ntiles = (b.out_row0 + b.out_rows - 1) / tile - tile_first + 1;
@@ -2109,6 +2128,7 @@ int run_axis0_mfma(const Block& b, double sigma, float* out, int table_slot, con
 int run_axis1_s1(GaussArgs a, int rows, int nx) {
     Context& c = ctx();
     const int nk = s1_steps(a.radius);
+    t_grad.s1_steps = nk;
     const int bands = (rows + 15) / 16, ntile = (nx + 31) / 32;
     // one block of 8 waves per CU; runs no shorter than 512 columns
     const int nseg = run_cut(bands, ntile, ntile / 16, 8L * c.num_cu, nk);
@@ -2137,6 +2157,7 @@ int run_axis1_mfma(const float* in, int rows, int nx, double sigma, float* out, 
     a.group0 = 1;  // every band turns its tile order by a number of tiles of its own (profiles/r04_pitch_spread.txt)
     const int steps = f16_steps(a.radius);
     if (split_once(steps)) return run_axis1_s1(a, rows, nx);
+    t_grad.tile_steps = steps;
     const int mt = f16_mt(true, a.radius);
     const int bands = (rows + 31) / 32;
     const int ntile = (nx + 32 * mt - 1) / (32 * mt), nunit = (nx + 31) / 32;
@@ -2196,6 +2217,7 @@ int run_fused_f16(const Block& b, double sigma, float* out, int table_slot, cons
     }
     a.wild_flag = const_cast<int*>(*flag_out);
     a.wild_host = dem_memo_wild_word(b);
+    t_grad.fused_steps = f16_steps(a.radius);
     const int tile_first = b.out_row0 / 32;
     const int ntile_rows = (b.out_row0 + b.out_rows - 1) / 32 - tile_first + 1;
     const int row_blocks = (ntile_rows + 3) / 4;
@@ -2235,6 +2257,7 @@ int run_axis0(const Block& b, double sigma, float* out, int table_slot, int mfma
     const int R = gaussian_radius(sigma);
     if (mfma_radius(R, b.nx, mfma_from) && mfma_rows_ok(b, R)) return run_axis0_mfma(b, sigma, out, table_slot);
     const int tb = wide_tiling(R) ? 16 : 8;
+    t_grad.valu_smooth = true;
     GaussArgs a;
     TOPO_TRY(gauss_args(b, out, sigma, tb, table_slot, &a));
     a.group0 = b.out_row0 / tb;
@@ -2275,6 +2298,7 @@ int run_axis1(const float* in, int rows, int nx, double sigma, float* out, int t
     const int R = gaussian_radius(sigma);
     if (mfma_radius(R, nx, mfma_from)) return run_axis1_mfma(in, rows, nx, sigma, out, table_slot);
     const bool wide = wide_tiling(R);
+    t_grad.valu_smooth = true;
     GaussArgs a;
     TOPO_TRY(gauss_args(plane_block(in, rows, nx), out, sigma, wide ? 16 : 8, table_slot, &a));
     if (wide) {
@@ -2347,6 +2371,9 @@ int launch_axis1_grad_pf(const GaussArgs& a, const GradArgs& g, size_t lds) {
     hipLaunchKernelGGL((gauss_axis1_grad_kernel<TB, KB, NW, PF>), dim3((unsigned)grid), dim3(NW * 64), lds, c.compute, a, g,
                        tiles_x, (int)ntiles);
     TOPO_HIP(hipGetLastError());
+    t_grad.finish = kGradFinishTiled;
+    t_grad.kb = KB;
+    t_grad.pf = PF;
     return TOPO_AMD_OK;
 }
 
@@ -2431,6 +2458,7 @@ int run_axis1_wave_grad(const float* in, int s_row0, int s_rows, double sigma, c
     dim3 grid((g.nx + a.out_c - 1) / a.out_c, (tiles + kThreads / 64 - 1) / (kThreads / 64));
     hipLaunchKernelGGL(gauss_axis1_wave_grad_kernel, grid, dim3(kThreads), 0, c.compute, a);
     TOPO_HIP(hipGetLastError());
+    if (!smooth_out) t_grad.finish = kGradFinishWave;  // (with a plane to write it is the smooth of run_axis1, no finish)
     return TOPO_AMD_OK;
 }
 
@@ -2558,6 +2586,8 @@ int launch_epilogue(GradArgs g, int rows, hipStream_t stream, const int* run_if 
     else if (run_if) hipLaunchKernelGGL(gradient_epilogue_if_kernel, grid, dim3(kThreads), 0, stream, g);
     else hipLaunchKernelGGL(gradient_epilogue_kernel, grid, dim3(kThreads), 0, stream, g);
     TOPO_HIP(hipGetLastError());
+    t_grad.epilogue = wide ? 2 : 1;
+    t_grad.rerun = t_grad.rerun || run_if != nullptr;
     return TOPO_AMD_OK;
 }
 
@@ -2565,6 +2595,15 @@ int launch_epilogue(GradArgs g, int rows, hipStream_t stream, const int* run_if 
 // TOPO_AMD_GRAD_CHUNK_MIN_ROWS output rows, else in one shot; elsewhere the vector-ALU kernels with axis 1 and the
 // epilogue fused.  Two sigmas (topo.py:633-635): two smooths.
 enum class GradRoute { Sobel, Chunked, Mfma, Valu, Aniso };
+// the code of include/topo_amd.h (topo_amd_gradient_route) for what t_grad holds
+int gradient_route_code(GradRoute route) {
+    const GradNote& n = t_grad;
+    const bool mfma = n.tile_steps || n.s1_steps;
+    const int smooth = n.fused_steps ? 1 : n.s1_steps ? 3 : n.tile_steps ? 2 : n.valu_smooth ? 4 : 0;
+    const int steps = n.fused_steps ? n.fused_steps : n.s1_steps ? n.s1_steps : n.tile_steps;
+    return (int)route | smooth << 3 | (n.valu_smooth && mfma ? 1 << 6 : 0) | steps << 7 | n.finish << 12 | (n.kb == 16 ? 1 << 14 : 0) |
+           n.pf << 15 | n.epilogue << 18 | (n.rerun ? 1 << 20 : 0) | (n.taper ? 1 << 21 : 0) | n.chunks << 22;
+}
 GradRoute gradient_route(const Block& b, double sigma, double sig_ratio, int mfma_from) {
     static const int chunk_min = [] {
         const char* e = std::getenv("TOPO_AMD_GRAD_CHUNK_MIN_ROWS");
@@ -2646,6 +2685,8 @@ int gradient_chunked(const Block& b, double sigma, const GradArgs& g) {
         c0 = c1;
     }
     TOPO_REQUIRE(chunks.size() <= 64, "gradient: %zu row chunks (at most 64)", chunks.size());
+    t_grad.chunks = (int)chunks.size();
+    t_grad.taper = taper;
     // Row shard: the chunks that stay clear of the ghost rows go first, on the rows the shard owns (the ghost rows are
     // being written meanwhile; staging clamps to the view), then the compute stream waits for the exchange and the
     // chunks at the two seams follow on the whole block - ordinary chunks of the ordinary pipeline, no seam strips
@@ -2745,6 +2786,15 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
     TOPO_REQUIRE(res_x && res_y, "gradient: resolution arrays are NULL");
     const bool large = large_sample_call();
     const GradRoute route = gradient_route(b, sigma, sig_ratio, mfma_from(large, true));
+    t_grad = GradNote{};  // (the Gaussian's launchers write it too: it means something only from here to noter.done)
+    // noted only when every launch of the call succeeded
+    struct Noter {
+        GradRoute route;
+        int done(int r) {
+            if (r == TOPO_AMD_OK) note_gradient_route(gradient_route_code(route));
+            return r;
+        }
+    } noter{route};
     // a row shard whose exchange is in flight (common.hpp, GhostGate): only the chunked route knows what to do with it;
     // every other route says so before it launches anything
     if (c.ghost.armed && route != GradRoute::Chunked) return TOPO_AMD_EUNSUP;
@@ -2766,12 +2816,12 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
         g.raw_row0 = b.in_row0;
         hipLaunchKernelGGL(sobel_kernel<true>, dim3((b.nx + kThreads - 1) / kThreads, b.out_rows), dim3(kThreads), 0, c.compute, g);
         TOPO_HIP(hipGetLastError());
-        return TOPO_AMD_OK;
+        return noter.done(TOPO_AMD_OK);
     }
     TOPO_REQUIRE(b.gny >= 2 && b.nx >= 2,
                  "gradient: numpy.gradient needs at least 2 samples per axis (got %d x %d)",
                  b.gny, b.nx);
-    if (route == GradRoute::Chunked) return gradient_chunked(b, sigma, g);
+    if (route == GradRoute::Chunked) return noter.done(gradient_chunked(b, sigma, g));
     const Block s = smoothed_rows_block(b);
     const size_t bytes = (size_t)s.out_rows * b.nx * sizeof(float);
     void *plane_a = nullptr, *plane_b = nullptr;
@@ -2785,14 +2835,15 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
         // beyond: 2.67 vs 3.63 ms at radius 32, 3.33 vs 4.07 at 56, 4.60 vs 5.17 at 92 on 16384^2
         if (gaussian_radius(sigma) <= fused_max) {
             const int r = run_axis1_grad((const float*)plane_a, s.out_row0, s.out_rows, b.gny, b.nx, sigma, g, 2);
-            if (r != TOPO_AMD_EUNSUP) return r;
+            if (r != TOPO_AMD_EUNSUP) return noter.done(r);
         }
         const int r = run_axis1_wave_grad((const float*)plane_a, s.out_row0, s.out_rows, sigma, g, nullptr);
-        if (r != TOPO_AMD_EUNSUP) return r;
+        if (r != TOPO_AMD_EUNSUP) return noter.done(r);
         // a filter wider than a wavefront can chain: finish the smooth unfused (beyond radius 121 axis 1 goes through
         // the wave-shift or the transpose path)
         TOPO_TRY(workspace(2, bytes, &plane_b));
         TOPO_TRY(run_axis1((const float*)plane_a, s.out_rows, b.nx, sigma, (float*)plane_b, 2, mfma_from(large, true)));
+        t_grad.finish = kGradFinishUnfused;
         plane_a = plane_b;
     } else if (route == GradRoute::Mfma) {  // the smooth of the chunked route (same kernels, same bits)
         TOPO_TRY(workspace(2, bytes, &plane_b));
@@ -2810,7 +2861,7 @@ int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode
     g.gy_src = (const float*)plane_b;
     g.s_row0 = s.out_row0;
     g.s_rows = s.out_rows;
-    return launch_epilogue(g, b.out_rows, c.compute);
+    return noter.done(launch_epilogue(g, b.out_rows, c.compute));
 }
 
 }  // namespace topo

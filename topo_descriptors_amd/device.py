@@ -159,6 +159,19 @@ def sx_route():
     return n.value
 
 
+def gradient_route():
+    """The kernels the calling thread's last gradient call queued (``topo_amd_gradient_route``, packed as ``include/topo_amd.h``
+    says): bits 0 - 2 the route (0 Sobel, 1 Chunked, 2 Mfma, 3 Valu, 4 Aniso); bits 3 - 5 the smooth (0 none, 1 fused f16 kernel
+    with the two passes queued behind its flag, 2 two-pass tile kernels, 3 two passes with split-once axis 1, 4 vector-ALU
+    axis 0), bit 6 Aniso with passes on both kinds of kernel, bits 7 - 11 the f16 step count; bits 12 - 13 the axis-1 finish of
+    the Valu route (1 LDS-tiled, 2 wave-shift, 3 unfused), bit 14 its tap chunks of 16, bits 15 - 17 its PF; bits 18 - 19 the
+    stand-alone epilogue (1 one pixel a thread, 2 four), bit 20 an ``_if`` rerun queued; bit 21 tapered chunks, bits 22 - 28
+    the number of row chunks."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().topo_amd_gradient_route(C.byref(n)), "gradient_route")
+    return n.value
+
+
 def dem_changed(array):
     """Tell the library that ``array`` (a :class:`DeviceArray`) was written by something other than the library."""
     _lib.check(_lib.lib().topo_amd_dem_changed(array.ptr, array.nbytes), "dem_changed")
