@@ -323,6 +323,28 @@ int topo_amd_sx_route(int* route);
  *   bit 21       the row chunks were tapered (first and last a quarter of the others).
  *   bits 22 - 28 the number of row chunks (0 unless Chunked).                                                             */
 int topo_amd_gradient_route(int* route);
+/* Which kernels the calling thread's last TPI / STD disc call queued (topo_amd_tpi_std_dev, topo_amd_tpi_multi_dev and the
+ * calls built on them; for tests and diagnostics): what the host decided, noted by the code that decided it once every
+ * launch of the call succeeded.  A call taller than one launch covers reports its last part (and bit 23); a multi-size call
+ * reports its last launch.  0: no disc call yet.
+ *   bits 0 - 2   the launcher: 1 the wave-shift kernels on the block as it is (odd sizes 3 ... 101), 2 the same on a copy
+ *                re-pitched to a multiple of 4 columns, 3 the LDS-gather kernel (even sizes, 1, odd sizes on fewer than 4
+ *                columns; below 70 px), 4 the prefix planes (from 70 px), 5 the two-disc kernel of topo_amd_tpi_multi_dev.
+ *   bit 3        TPI was wanted.        bit 4: STD was wanted.
+ *   bits 5 - 8   the first kernel over the whole-metre tiles (launchers 1, 2, 5): 0 none (the general kernel alone over every
+ *                tile), 1 tpi_march, 2 the TPI ring (marking), 3 the wide ring, 4 the scaled march taking every tile, 5 the
+ *                STD ring, 6 the STD ring with staging waves apart, 4 columns a lane, 7 the same with 8 columns a lane,
+ *                8 the marching sums of the three-pass route, 9 the TPI ring of two discs.
+ *   bit 9        std_march followed.
+ *   bits 10 - 12 the second pass over the tiles with fractional samples: 0 none, 1 fraction_march, 2 the TPI ring with two
+ *                images, 3 the STD ring with three images, 4 the same with staging waves apart.
+ *   bit 13       scaled_march followed.        bit 14: the general kernel followed over the tiles left marked.
+ *   bits 16 - 22 the tile height of the first kernel (launcher 3: of the gather kernel; launcher 4: 0).
+ *   bit 23       the call was split by rows (more rows than one launch covers).
+ *   bit 24       the value of topo_amd_tpi_route.
+ *   bit 25       launcher 4: the float64 planes (a sample that is not finite or beyond +-65536).
+ *   bit 26       launcher 4: the narrow planes' kernel with the plane of fractional parts.                                */
+int topo_amd_disc_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);

@@ -50,6 +50,7 @@ SIGNATURES = {
     "topo_amd_tpi_route": (C.c_int, [_i32p]),
     "topo_amd_sx_route": (C.c_int, [_i32p]),
     "topo_amd_gradient_route": (C.c_int, [_i32p]),
+    "topo_amd_disc_route": (C.c_int, [_i32p]),
     "topo_amd_dem_changed": (C.c_int, [_vp, C.c_size_t]),
     "topo_amd_raster_scan_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_uint64), _f32p]),

@@ -533,6 +533,7 @@ thread_local int t_tpi_route = 0;     // 1: the calling thread's last TPI / STD 
 thread_local int t_valley_route = 0;  // the evaluation the calling thread's last valley / ridge call took (topo_amd_valley_route)
 thread_local int t_sx_route = 0;      // the kernel route the calling thread's last Sx call took (topo_amd_sx_route)
 thread_local int t_gradient_route = 0;  // the same of its last gradient call (topo_amd_gradient_route)
+thread_local int t_disc_route = 0;      // the same of its last TPI / STD disc call (topo_amd_disc_route)
 thread_local int t_host_chunks = 0;  // row chunks of the calling thread's last host-buffer call (topo_amd_host_chunks)
 struct HostRun {
     std::vector<void*> bufs;
@@ -873,6 +874,8 @@ void note_tpi_route(int route) { t_tpi_route = route; }
 void note_valley_route(int route) { t_valley_route = route; }
 void note_sx_route(int route) { t_sx_route = route; }
 void note_gradient_route(int route) { t_gradient_route = route; }
+void note_disc_route(int route) { t_disc_route = route; }
+int noted_disc_route() { return t_disc_route; }
 
 }  // namespace topo
 
@@ -1107,6 +1110,12 @@ int topo_amd_sx_route(int* route) {
 int topo_amd_gradient_route(int* route) {
     TOPO_REQUIRE(route != nullptr, "gradient_route: NULL output");
     *route = t_gradient_route;
+    return TOPO_AMD_OK;
+}
+
+int topo_amd_disc_route(int* route) {
+    TOPO_REQUIRE(route != nullptr, "disc_route: NULL output");
+    *route = (t_disc_route & ~kDiscWideRing) | (t_tpi_route ? kDiscWideRing : 0);  // (the bit IS topo_amd_tpi_route)
     return TOPO_AMD_OK;
 }
 

@@ -234,6 +234,26 @@ void note_tpi_route(int route);     // what topo_amd_tpi_route reports for the c
 void note_valley_route(int route);  // what topo_amd_valley_route reports for the calling thread (capi.hip)
 void note_sx_route(int route);      // what topo_amd_sx_route reports for the calling thread (capi.hip)
 void note_gradient_route(int route);  // what topo_amd_gradient_route reports for the calling thread (capi.hip)
+// What topo_amd_disc_route reports for the calling thread (include/topo_amd.h has the layout).  The host code that picked
+// the kernels notes the word once its launches succeeded; the launchers around it put their own bits into the noted word.
+enum DiscRoute : int {
+    kDiscWave = 1, kDiscRepitched = 2, kDiscGather = 3, kDiscPlanes = 4, kDiscPair = 5, kDiscLauncherMask = 7,
+    kDiscTpi = 1 << 3, kDiscStd = 1 << 4,
+    kDiscFirstGeneral = 0 << 5, kDiscFirstMarch = 1 << 5, kDiscFirstRing = 2 << 5, kDiscFirstWide = 3 << 5,
+    kDiscFirstScaledAll = 4 << 5, kDiscFirstStdRing = 5 << 5, kDiscFirstSpec4 = 6 << 5, kDiscFirstSpec8 = 7 << 5,
+    kDiscFirstSums = 8 << 5, kDiscFirstPairRing = 9 << 5,
+    kDiscStdMarch = 1 << 9,
+    kDiscFracMarch = 1 << 10, kDiscFracRingBoth = 2 << 10, kDiscFracStdRingBoth = 3 << 10, kDiscFracSpecBoth = 4 << 10,
+    kDiscScaledMarch = 1 << 13, kDiscDeferred = 1 << 14,
+    kDiscTileShift = 16,  // bits 16 - 22: the tile height of the first kernel
+    kDiscSplit = 1 << 23, kDiscWideRing = 1 << 24, kDiscPlanesF64 = 1 << 25, kDiscPlanesFrac = 1 << 26,
+};
+void note_disc_route(int route);
+int noted_disc_route();
+inline int note_disc_if_ok(int rc, int route) {  // for the last launch of a route: `return note_disc_if_ok(launch(...), word)`
+    if (rc == TOPO_AMD_OK) note_disc_route(route);
+    return rc;
+}
 // the same on the matrix pipe for rotated kernels of up to kValleyMfmaMaxKernel cells a side with at most 240 cells that hold a
 // tap at any angle (valley_mfma.hip; *done = 0: not such a case, nothing launched); leaves the pixels it cannot do marked
 // norm = g.mark and their tiles (kValleyMfmaTileRows x 64, anchored at out_row0) flagged.  n_planes (1..4): planes g.p0 ...

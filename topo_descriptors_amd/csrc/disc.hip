@@ -396,6 +396,8 @@ int launch_disc_wave_repitched(const Block& b, int size, float* tpi_out, float* 
     if (tpi_out) TOPO_TRY(workspace(5, (size_t)b.out_rows * nxp * sizeof(float), &tpi_p));
     if (std_out) TOPO_TRY(workspace(6, (size_t)b.out_rows * nxp * sizeof(float), &std_p));
     TOPO_TRY(repitch(b.in, b.nx, (float*)in_p, nxp, b.nx, nxp, b.in_rows));
+    // (the workspace holds another plane now: what the last call on it left about its tiles would pick this call's first kernel)
+    dem_memo_forget(in_p, (size_t)b.in_rows * nxp * sizeof(float));
     Block bp = b;
     bp.in = (const float*)in_p;
     bp.nx = nxp;
@@ -403,6 +405,7 @@ int launch_disc_wave_repitched(const Block& b, int size, float* tpi_out, float* 
     if (r != TOPO_AMD_OK) return r;
     if (tpi_out) TOPO_TRY(repitch((const float*)tpi_p, nxp, tpi_out, b.nx, b.nx, b.nx, b.out_rows));
     if (std_out) TOPO_TRY(repitch((const float*)std_p, nxp, std_out, b.nx, b.nx, b.nx, b.out_rows));
+    note_disc_route((noted_disc_route() & ~kDiscLauncherMask) | kDiscRepitched);
     return TOPO_AMD_OK;
 }
 
@@ -417,6 +420,7 @@ int launch_tpi_std(const Block& b, const DiscRuns& disc, float* tpi_out, float* 
             s.out_rows = std::min(kMaxLaunchRows, b.out_rows - r);
             TOPO_TRY(launch_tpi_std(s, disc, tpi_out ? tpi_out + (size_t)r * b.nx : nullptr, std_out ? std_out + (size_t)r * b.nx : nullptr));
         }
+        note_disc_route(noted_disc_route() | kDiscSplit);  // (the word of the last part)
         return TOPO_AMD_OK;
     }
     TOPO_REQUIRE(tpi_out || std_out, "tpi_std: both outputs are NULL");
@@ -484,10 +488,11 @@ int launch_tpi_std(const Block& b, const DiscRuns& disc, float* tpi_out, float* 
               (b.out_row0 + b.out_rows - 1) / tile_h - b.out_row0 / tile_h + 1);
     const size_t lds = lds_for(tile_h);
     const bool tpi = tpi_out != nullptr, sd = std_out != nullptr;
+    const int word = kDiscGather | (tpi ? kDiscTpi : 0) | (sd ? kDiscStd : 0) | (tile_h << kDiscTileShift);
     switch (tile_h) {
-        case 32: return launch_tile<32>(a, grid, lds, c.compute, tpi, sd);
-        case 16: return launch_tile<16>(a, grid, lds, c.compute, tpi, sd);
-        default: return launch_tile<8>(a, grid, lds, c.compute, tpi, sd);
+        case 32: return note_disc_if_ok(launch_tile<32>(a, grid, lds, c.compute, tpi, sd), word);
+        case 16: return note_disc_if_ok(launch_tile<16>(a, grid, lds, c.compute, tpi, sd), word);
+        default: return note_disc_if_ok(launch_tile<8>(a, grid, lds, c.compute, tpi, sd), word);
     }
 }
 

@@ -326,6 +326,7 @@ int launch_disc_big(const Block& b, const DiscRuns& disc, float* tpi_out, float*
     void* d_runs = nullptr;
     TOPO_TRY(upload_table(0, packed.data(), packed.size() * sizeof(int), &d_runs));
     a.runs = (const int*)d_runs;
+    const int word = kDiscPlanes | (tpi_out ? kDiscTpi : 0) | (std_out ? kDiscStd : 0);  // topo_amd_disc_route
     TOPO_TRY(check_grid_rows(std::max(b.out_rows, b.in_rows), "disc (prefix planes)"));
     const dim3 pgrid((b.nx + kThreads - 1) / kThreads), ggrid((b.nx + kThreads - 1) / kThreads, b.out_rows);
 
@@ -356,6 +357,7 @@ int launch_disc_big(const Block& b, const DiscRuns& disc, float* tpi_out, float*
         else if (tpi_out) frac ? go(big_disc_int_kernel<true, false, true>) : go(big_disc_int_kernel<true, false, false>);
         else frac ? go(big_disc_int_kernel<false, true, true>) : go(big_disc_int_kernel<false, true, false>);
         TOPO_HIP(hipGetLastError());
+        note_disc_route(word | (frac ? kDiscPlanesFrac : 0));
         return TOPO_AMD_OK;
     }
     // non-finite or absurd samples: float64 planes, so that NaN propagates and nothing wraps
@@ -375,6 +377,7 @@ int launch_disc_big(const Block& b, const DiscRuns& disc, float* tpi_out, float*
     else if (tpi_out) hipLaunchKernelGGL((big_disc_kernel<true, false>), grid, dim3(kThreads), 0, c.compute, a);
     else hipLaunchKernelGGL((big_disc_kernel<false, true>), grid, dim3(kThreads), 0, c.compute, a);
     TOPO_HIP(hipGetLastError());
+    note_disc_route(word | kDiscPlanesF64);
     return TOPO_AMD_OK;
 }
 

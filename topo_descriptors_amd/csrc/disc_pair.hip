@@ -17,7 +17,9 @@ int launch_pair(const Block& b, float* out_b, float* out_a) {
     constexpr int map_tw = RGeo<SB, 8>::TILE_W;
     TOPO_TRY((launch_ring<SB, 8, kRingMain, SA>(b, out_b, out_a)));
     TOPO_TRY((launch_wave<SB, tile_rows(SB, 12, 60), 12, true, false>(b, out_b, nullptr, true, RC::TH, map_tw)));
-    return launch_wave<SA, tile_rows(SA, 12, 60), 12, true, false>(b, out_a, nullptr, true, RC::TH, map_tw);
+    note_tpi_route(0);  // (a disc call that is not the wide ring's)
+    return note_disc_if_ok(launch_wave<SA, tile_rows(SA, 12, 60), 12, true, false>(b, out_a, nullptr, true, RC::TH, map_tw),
+                           kDiscPair | kDiscTpi | kDiscFirstPairRing | (RC::TH << kDiscTileShift) | kDiscDeferred);
 }
 
 }  // namespace

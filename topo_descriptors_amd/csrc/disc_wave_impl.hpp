@@ -2290,6 +2290,9 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
     // The marching kernels take the tiles of whole metres, the general kernel the tiles they left
     // (none on a DEM of whole metres; all of them on one with fractional elevations).
     constexpr bool kFullTile = TH12 == 60;  // LDS holds the tile height the marching kernels were tuned for
+    // what topo_amd_disc_route reports: the first kernel over the whole-metre tiles, its tile height, the followers queued
+    const int wanted = kDiscWave | (tpi_out ? kDiscTpi : 0) | (std_out ? kDiscStd : 0);
+    const auto route = [wanted](int first, int th, int followers) { return wanted | first | (th << kDiscTileShift) | followers; };
     if constexpr (std_ring_fits(SIZE) && !std_ring_both_fits(SIZE) && kFullTile) {
         // STD (and TPI + STD) on a raster of mostly fractional elevations, discs of 43 ... 67 px (below, the ring kernel has
         // a three-image second pass; here three images do not fit LDS and every tile used to end with the general kernel's
@@ -2303,8 +2306,9 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
             else TOPO_TRY((launch_march_sums<SIZE, TH12, 12, false>(b, nullptr)));
             TOPO_TRY((launch_std_march<SIZE, TH12, 12, true>(b, std_out)));
             TOPO_TRY((launch_fraction_march<SIZE, TH12, 12, true>(b, tpi_out, std_out)));
-            if (tpi_out) return launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12);
-            return launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12);
+            const int word = route(kDiscFirstSums, TH12, kDiscStdMarch | kDiscFracMarch | kDiscDeferred);
+            if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12), word);
+            return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12), word);
         }
     }
     if constexpr (std_ring_fits(SIZE)) {
@@ -2327,8 +2331,9 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
                 if (current_class().frac_share == 0.0f && std_spec_wide() && (tpi_out != nullptr || (SIZE <= 7 && big))) {
                     if (tpi_out) TOPO_TRY((launch_std_ring_spec<SIZE, true, false, 8>(b, tpi_out, std_out)));
                     else TOPO_TRY((launch_std_ring_spec<SIZE, false, false, 8>(b, nullptr, std_out)));
-                    if (tpi_out) return launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W);
-                    return launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W);
+                    const int word = route(kDiscFirstSpec8, StdRingCfg<SIZE>::TH, kDiscDeferred);
+                    if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W), word);
+                    return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W), word);
                 }
             }
             if constexpr (std_ring_spec(SIZE)) {  // the small discs: staging waves apart from chain waves
@@ -2349,15 +2354,17 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
                     else TOPO_TRY((launch_std_ring<SIZE, false, kStdBoth>(b, nullptr, std_out)));
                 }
             }
-            if (tpi_out) return launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH);
-            return launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH);
+            const int word = route(std_ring_spec(SIZE) ? kDiscFirstSpec4 : kDiscFirstStdRing, StdRingCfg<SIZE>::TH,
+                                   (!std_ring_both_fits(SIZE) ? 0 : std_spec_both_fits(SIZE) ? kDiscFracSpecBoth : kDiscFracStdRingBoth) | kDiscDeferred);
+            if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH), word);
+            return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH), word);
         }
     }
     if (std_out && (SIZE < std_march_min_size() || !kFullTile)) {
         // small discs: one general kernel (two passes per tile, the second one out of L2) moves three
         // planes where the marching pair moves five, and the chains are too short to matter
-        if (tpi_out) return launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out);
-        return launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out);
+        if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH8, 0));
+        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH8, 0));
     }
     if (std_out) {
         // sum x (and TPI) marching, then sum u^2 -> STD marching over the same runs, then the
@@ -2368,10 +2375,11 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
             TOPO_TRY((launch_march<SIZE, TH12, 12, false, true>(b, nullptr)));
         }
         TOPO_TRY((launch_std_march<SIZE, TH12, 12>(b, std_out)));
-        if (tpi_out) return launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12);
-        return launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12);
+        const int word = route(kDiscFirstMarch, TH12, kDiscStdMarch | kDiscDeferred);
+        if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12), word);
+        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12), word);
     }
-    if (SIZE < tpi_march_min_size()) return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out);
+    if (SIZE < tpi_march_min_size()) return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH12, 0));
     // TPI alone: whole-metre tiles are finished by the first marching kernel; tiles with fractional
     // elevations get their exact sum of trunc(x) there and the sum of the fractional parts in the
     // second; the general kernel takes what neither could (non-finite or absurd samples)
@@ -2386,13 +2394,14 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
             // DEM with fractional elevations: 7 px 5.36 -> 2.48 ms, 17 px 5.31 -> 3.79 ms (profiles/r03_tpi_ring_both.txt)
             TOPO_TRY((launch_ring<SIZE, 8, kRingMark>(b, tpi_out)));
             TOPO_TRY((launch_ring<SIZE, 8, kRingBoth>(b, tpi_out)));
-            return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true, RC::TH, map_tw);
+            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true, RC::TH, map_tw),
+                                   route(kDiscFirstRing, RC::TH, kDiscFracRingBoth | kDiscDeferred));
         }
     }
     if (SIZE < tpi_fraction_min_size()) {
         // small discs: the general kernel's two passes over one tile beat two marching kernels
         TOPO_TRY((launch_march<SIZE, TH12, 12, true, false, false>(b, tpi_out)));
-        return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+        return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscDeferred));
     }
     if constexpr (tpi_wide_ring_fits(SIZE) && SIZE >= tpi_wide_min_size() && SIZE <= tpi_wide_max_size()) {
         // whole metres, one block: the wide ring computes the phases whose windows hold whole metres and marks the marching
@@ -2404,7 +2413,8 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
             TOPO_TRY((launch_ring_wide<SIZE>(b, tpi_out, TH12, Geo<SIZE>::TILE_W)));
             note_tpi_route(1);
             TOPO_TRY((launch_scaled_march<SIZE, TH12, 12>(b, tpi_out)));
-            return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true),
+                                   route(kDiscFirstWide, WideCfg<SIZE>::TH, kDiscScaledMarch | kDiscDeferred | kDiscWideRing));
         }
     }
     if (tpi_fraction_scaled()) {
@@ -2413,15 +2423,15 @@ int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
         // raster class says: the scaled build takes every tile)
         if (dem_memo_mostly_fractional(b) || current_class().frac_share > 0.5f) {
             TOPO_TRY((launch_scaled_march<SIZE, TH12, 12, true>(b, tpi_out)));
-            return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstScaledAll, TH12, kDiscDeferred));
         }
         TOPO_TRY((launch_march<SIZE, TH12, 12, true, true, true>(b, tpi_out, true)));
         TOPO_TRY((launch_scaled_march<SIZE, TH12, 12>(b, tpi_out)));
-        return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+        return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscScaledMarch | kDiscDeferred));
     }
     TOPO_TRY((launch_march<SIZE, TH12, 12, true, true, true>(b, tpi_out)));
     TOPO_TRY((launch_fraction_march<SIZE, TH12, 12>(b, tpi_out)));
-    return launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true);
+    return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscFracMarch | kDiscDeferred));
 }
 
 }  // namespace

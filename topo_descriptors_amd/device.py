@@ -172,6 +172,18 @@ def gradient_route():
     return n.value
 
 
+def disc_route():
+    """The kernels the calling thread's last TPI / STD disc call queued (``topo_amd_disc_route``, packed as ``include/topo_amd.h``
+    says): bits 0 - 2 the launcher (1 wave-shift kernels, 2 the same on a re-pitched copy, 3 LDS gather, 4 prefix planes, 5 the
+    two-disc kernel), bit 3 / 4 TPI / STD wanted, bits 5 - 8 the first kernel over the whole-metre tiles, bit 9 ``std_march``,
+    bits 10 - 12 the second pass over fractional tiles, bit 13 ``scaled_march``, bit 14 the deferred general kernel, bits
+    16 - 22 the first kernel's tile height, bit 23 split by rows, bit 24 ``tpi_route()``, bits 25 / 26 the float64 / the
+    fractional prefix planes."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().topo_amd_disc_route(C.byref(n)), "disc_route")
+    return n.value
+
+
 def dem_changed(array):
     """Tell the library that ``array`` (a :class:`DeviceArray`) was written by something other than the library."""
     _lib.check(_lib.lib().topo_amd_dem_changed(array.ptr, array.nbytes), "dem_changed")
