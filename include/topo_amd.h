@@ -470,6 +470,62 @@ int topo_amd_valley_ridge_raw(const topo_amd_raster* src, int ny, int nx, const 
                               const float* angles, int n_angles, int n_planes, double mean, double stdev, float* norm_out,
                               float* dir_out);
 
+/* ---- packed result planes: a result encoded on the GPU, downloaded as the file will store it -----------------------------
+ * The users' files hold these quantities packed - CF scale_factor / add_offset / _FillValue in netCDF, int16 in GeoTIFF -
+ * and a host-buffer call is bound by the link: a topo_amd_plane describes a result array of 1 or 2 bytes a sample, and the
+ * *_packed entry points encode each row chunk of the float32 device plane behind its kernels (csrc/encode.hip) and download
+ * the packed rows.  The encode of a float32 sample v into an integer type T, [lo, hi] being T's range without `nodata`:
+ *
+ *     code = nodata                                  if v is NaN                      (counted in `missing`)
+ *     q    = rint( ((double)v - offset) / scale )    otherwise
+ *     code = lo if q < lo, hi if q > hi              (+-inf included; counted in `saturated`)
+ *     code = (T) q                                   otherwise
+ *
+ * The difference and the quotient are each rounded in float64 (a true division, no reciprocal), rint rounds to
+ * nearest-even.  has_nodata is required and nodata must be T's lowest or highest code (-32768 or 32767, 0 or 65535, 0 or
+ * 255), so no value is ever stored as the nodata code: decode(encode(v)) is NaN exactly where v is NaN.  scale finite and
+ * not 0, offset finite.
+ * TOPO_AMD_F16: IEEE binary16, round to nearest-even; scale 1, offset 0, no nodata; NaN is stored as 0x7E00 (counted in
+ * `missing`), a finite sample that becomes +-inf is counted in `saturated`.  A code for result planes only: as a source
+ * dtype it is TOPO_AMD_EINVAL.
+ * TOPO_AMD_F32: scale 1, offset 0, no nodata; the plane is passed through - no encode runs, no extra device plane is
+ * taken, both counters are 0.  The *_raw entry points are the *_packed ones called with such planes.
+ * Anything else (I32, F64, an unknown dtype, a nodata inside the range) is TOPO_AMD_EINVAL.
+ * Sobel, fill_na and the valley / ridge index stay float32-only: topo_amd_valley_ridge_* is one chunk by design and its
+ * planes are small next to its run time.  Row shards encode their device planes with topo_amd_encode_dev.                */
+#define TOPO_AMD_F16 6
+typedef struct topo_amd_plane {
+    void* data;         /* host, ny x nx samples of dtype, C-contiguous; NULL where the _raw namesake allows NULL */
+    int32_t dtype;      /* TOPO_AMD_F32, _I16, _U16, _U8, _F16 */
+    int32_t has_nodata;
+    double scale, offset, nodata;
+    uint64_t missing;   /* out: samples stored as nodata / NaN */
+    uint64_t saturated; /* out: samples clamped (integer types) or overflowed to inf (F16) */
+} topo_amd_plane;
+/* The formula above on the host, one thread: count floats at `in` -> plane->data.  Needs no GPU and no topo_amd_init.    */
+int topo_amd_encode_host(const float* in, size_t count, topo_amd_plane* plane);
+/* The same on the device: plane->data is a DEVICE address aligned to the sample type (16-byte accesses where it shares a
+ * 16-byte phase with in_dev, sample by sample otherwise).  Enqueued on the compute stream; the call returns when the
+ * counters are valid (it waits for the stream).                                                                          */
+int topo_amd_encode_dev(const float* in_dev, size_t count, topo_amd_plane* plane);
+/* The host-buffer entry points with packed result planes: as their *_raw namesakes with a topo_amd_plane in place of every
+ * float* (NULL, or a plane whose data is NULL, where the namesake allows NULL) and an array of n planes in place of every
+ * float* const*.  Every plane is, bit for bit, topo_amd_encode_host of the float32 plane the *_raw call gives; the counters
+ * of each plane are written when the call returns.                                                                       */
+int topo_amd_tpi_std_packed(const topo_amd_raster* src, int ny, int nx, int size, double sigma, topo_amd_plane* tpi_out,
+                            topo_amd_plane* std_out);
+int topo_amd_tpi_std_multi_packed(const topo_amd_raster* src, int ny, int nx, int n_scales, const int32_t* sizes,
+                                  const double* sigmas, topo_amd_plane* tpi_outs, topo_amd_plane* std_outs);
+int topo_amd_gauss_packed(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, topo_amd_plane* out);
+int topo_amd_gradient_packed(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
+                             const void* res_x, const void* res_y, topo_amd_plane* dx_out, topo_amd_plane* dy_out,
+                             topo_amd_plane* slope_out, topo_amd_plane* aspect_out);
+int topo_amd_sx_packed(const topo_amd_raster* src, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist,
+                       int n_off, int window, double height, topo_amd_plane* out);
+int topo_amd_sx_multi_packed(const topo_amd_raster* src, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,
+                             const int32_t* di, const double* dist, const int32_t* window, double height,
+                             topo_amd_plane* outs);
+
 /* ---- row sharding over the GPUs of one node (RCCL over xGMI) -------------------------- */
 /* The reference's only precedent is dask map_overlap(depth, boundary="none") for TPI
  * (topo.py:177-178): independent blocks plus ghost rows.  Rank r owns a contiguous row

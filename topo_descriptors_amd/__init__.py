@@ -20,7 +20,7 @@ class _Config:
 CFG = _Config()
 
 from . import helpers, topo  # noqa: E402,F401
-from ._lib import PackedDem  # noqa: E402,F401
+from ._lib import PackedDem, PackedPlane, Packing  # noqa: E402,F401
 
 
 def release_host_planes():

@@ -21,11 +21,23 @@ class Raster(C.Structure):
                 ("scale", C.c_double), ("offset", C.c_double), ("nodata", C.c_double)]
 
 
+class Plane(C.Structure):
+    """``topo_amd_plane`` (include/topo_amd.h): a result array as a file stores it, how float32 samples encode into it, and
+    the two counters the encode reports."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("has_nodata", C.c_int32),
+                ("scale", C.c_double), ("offset", C.c_double), ("nodata", C.c_double),
+                ("missing", C.c_uint64), ("saturated", C.c_uint64)]
+
+
 _rp = C.POINTER(Raster)
+_pp = C.POINTER(Plane)
 # numpy dtype -> TOPO_AMD_F32 ... TOPO_AMD_F64
 F32, I16, U16, I32, U8, F64 = range(6)
 SOURCE_DTYPES = {np.dtype(np.float32): F32, np.dtype(np.int16): I16, np.dtype(np.uint16): U16,
                  np.dtype(np.int32): I32, np.dtype(np.uint8): U8, np.dtype(np.float64): F64}
+F16 = 6  # TOPO_AMD_F16: result planes only
+PLANE_DTYPES = {np.dtype(np.float32): F32, np.dtype(np.int16): I16, np.dtype(np.uint16): U16, np.dtype(np.uint8): U8,
+                np.dtype(np.float16): F16}
 
 # name -> (restype, argtypes); every symbol include/topo_amd.h declares
 SIGNATURES = {
@@ -120,6 +132,17 @@ SIGNATURES = {
                                   C.c_double, _vp]),
     "topo_amd_sx_multi_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _i32p,
                                         C.c_double, C.POINTER(_vp)]),
+    "topo_amd_encode_host": (C.c_int, [_vp, C.c_size_t, _pp]),
+    "topo_amd_encode_dev": (C.c_int, [_vp, C.c_size_t, _pp]),
+    "topo_amd_tpi_std_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _pp, _pp]),
+    "topo_amd_tpi_std_multi_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _pp, _pp]),
+    "topo_amd_gauss_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, _pp]),
+    "topo_amd_gradient_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                           _vp, _vp, _pp, _pp, _pp, _pp]),
+    "topo_amd_sx_packed": (C.c_int, [_rp, C.c_int, C.c_int, _i32p, _i32p, _f64p, C.c_int, C.c_int,
+                                     C.c_double, _pp]),
+    "topo_amd_sx_multi_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _i32p,
+                                           C.c_double, _pp]),
     "topo_amd_shard_sx_multi": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
                                           _i32p, _f64p, _i32p, C.c_double, C.POINTER(_vp)]),
     "topo_amd_shard_valley_ridge": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int,
@@ -256,3 +279,103 @@ def source_of(values):
     if isinstance(values, PackedDem):
         return values.source()
     return as_source(values)
+
+
+# ---- packed result planes (include/topo_amd.h, "packed result planes") --------------------------------------------------------
+class Packing:
+    """How a float32 result plane is to be stored: ``dtype`` int16, uint16 or uint8 with CF's ``scale_factor``,
+    ``add_offset`` and a ``fill_value`` for NaN - which must be the type's lowest or highest code, so that no value is ever
+    stored as it - or float16 (no scale, no offset, no fill value: NaN stays NaN), or float32 (the plane as it is).  A sample
+    ``v`` becomes ``rint((float64(v) - add_offset) / scale_factor)``, clamped to the codes that are left.  The request is
+    checked here, on the host, with the library's rules: ``ValueError`` before any library call."""
+
+    def __init__(self, dtype, scale_factor=1.0, add_offset=0.0, fill_value=None):
+        try:
+            self.dtype = np.dtype(dtype)
+        except TypeError as exc:
+            raise ValueError(f"Packing: {dtype!r} is not a dtype") from exc
+        if self.dtype not in PLANE_DTYPES or not self.dtype.isnative:
+            raise ValueError(f"Packing: result planes are int16, uint16, uint8, float16 or float32, not {self.dtype}")
+        self.scale_factor, self.add_offset = float(scale_factor), float(add_offset)
+        self.fill_value = None if fill_value is None else float(fill_value)
+        if not np.isfinite(self.scale_factor) or self.scale_factor == 0.0:
+            raise ValueError(f"Packing: scale_factor {self.scale_factor} (it must be finite and not 0)")
+        if not np.isfinite(self.add_offset):
+            raise ValueError(f"Packing: add_offset {self.add_offset} is not finite")
+        if self.dtype.kind == "f":
+            if self.scale_factor != 1.0 or self.add_offset != 0.0 or self.fill_value is not None:
+                raise ValueError(f"Packing: a {self.dtype} plane takes scale_factor 1, add_offset 0 and no fill_value")
+        else:
+            info = np.iinfo(self.dtype)
+            if self.fill_value is None:
+                raise ValueError(f"Packing: an {self.dtype} plane needs a fill_value (NaN has no other place)")
+            if self.fill_value not in (float(info.min), float(info.max)):
+                raise ValueError(f"Packing: fill_value {self.fill_value} must be the lowest or highest code of {self.dtype} "
+                                 f"({info.min} or {info.max})")
+
+    def __repr__(self):
+        return f"Packing({self.dtype}, {self.scale_factor}, {self.add_offset}, {self.fill_value})"
+
+    def struct(self, address):
+        """The ``Plane`` of an array of this packing at ``address`` (host or device)."""
+        return Plane(address, PLANE_DTYPES[self.dtype], int(self.fill_value is not None), self.scale_factor, self.add_offset,
+                     0.0 if self.fill_value is None else self.fill_value, 0, 0)
+
+
+class PackedPlane(PackedDem):
+    """A result plane as it came off the GPU: ``values`` (int16 / uint16 / uint8 codes, float16 or float32) with the CF triple
+    of its :class:`Packing`, ``missing`` (samples stored as the fill value, or NaN for float16) and ``saturated`` (samples
+    clamped to the end of the code range, or finite ones that became inf in float16).  It is a :class:`PackedDem`:
+    ``decode()`` gives the float32 array - NaN exactly where the result was NaN - and it can go straight back in as a source
+    (a packed smoothed DEM into ``topo.tpi``)."""
+
+    def __init__(self, values, packing, missing=0, saturated=0):
+        super().__init__(values, packing.scale_factor, packing.add_offset, packing.fill_value)
+        self.packing = packing
+        self.missing, self.saturated = int(missing), int(saturated)
+
+
+def result_plane(packing, shape):
+    """``(array, Plane)`` of one result of a ``*_packed`` call: an uninitialised array of the packing's dtype (``None``:
+    float32) and the struct that points into it."""
+    packing = Packing(np.float32) if packing is None else packing
+    array = np.empty(shape, dtype=packing.dtype)
+    return array, packing.struct(array.ctypes.data)
+
+
+def wrap_plane(array, plane, packing):
+    """What a ``pack=`` call returns for one plane: the float32 array for ``None``, a :class:`PackedPlane` otherwise."""
+    return array if packing is None else PackedPlane(array, packing, plane.missing, plane.saturated)
+
+
+def plane_array(structs):
+    """A C array of ``Plane`` from a list of structs (the ``topo_amd_plane*`` of the multi-plane calls)."""
+    return (Plane * len(structs))(*structs)
+
+
+def encode_host(array, packing):
+    """``array`` (float32) packed on the host (``topo_amd_encode_host``; one thread): the CPU statement of what the GPU does."""
+    a = as_f32(array)
+    out, plane = result_plane(packing, a.shape)
+    check(load().topo_amd_encode_host(ptr(a), a.size, C.byref(plane)), "topo_amd_encode_host")
+    return PackedPlane(out, packing, plane.missing, plane.saturated)
+
+
+def pack_list(pack, names):
+    """One packing (or ``None``: float32) per plane of a call from its ``pack`` argument: a single :class:`Packing` for all
+    planes, a sequence with one entry per plane, or a dict keyed by ``names``."""
+    if pack is None or isinstance(pack, Packing):
+        out = [pack] * len(names)
+    elif isinstance(pack, dict):
+        unknown = set(pack) - set(names)
+        if unknown:
+            raise ValueError(f"pack: unknown planes {sorted(map(str, unknown))}; the planes are {list(names)}")
+        out = [pack.get(n) for n in names]
+    else:
+        out = list(pack)
+        if len(out) != len(names):
+            raise ValueError(f"pack: {len(out)} entries for {len(names)} planes")
+    for q in out:
+        if q is not None and not isinstance(q, Packing):
+            raise ValueError(f"pack: {q!r} is not a Packing")
+    return out

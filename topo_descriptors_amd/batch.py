@@ -50,23 +50,36 @@ def _sx_name(radius, azimuth):
 
 # ---- writer ------------------------------------------------------------------------------------
 def write_output(array, dem_ds, name, crop=None, outdir=".", units=None):
-    """``hlp.to_netcdf`` of the reference (helpers.py:34-65) when xarray is there, .npy otherwise."""
+    """``hlp.to_netcdf`` of the reference (helpers.py:34-65) when xarray is there, .npy otherwise.  A ``PackedPlane`` goes
+    into the netCDF file with its packing as the variable's encoding, or into ``topo_<NAME>.npz`` (``values``,
+    ``scale_factor``, ``add_offset``, ``fill_value``: NaN for none)."""
     name = str.upper(name)
     if outdir is None:
         return None
     os.makedirs(outdir, exist_ok=True)
+    packed = array if isinstance(array, _lib.PackedPlane) else None
     if hlp._xr is not None and isinstance(dem_ds, hlp._xr.Dataset):  # pragma: no cover
-        ds = hlp._xr.Dataset({name: (hlp.get_da(dem_ds).dims, array)}, coords=dem_ds.coords,
+        ds = hlp._xr.Dataset({name: (hlp.get_da(dem_ds).dims, packed.decode() if packed else array)}, coords=dem_ds.coords,
                              attrs=dem_ds.attrs).sel(crop)
         if units is not None:
             ds[name].attrs.update(units=units)
+        if packed:
+            enc = {"dtype": packed.values.dtype}
+            if packed.values.dtype.kind != "f":
+                enc.update(scale_factor=packed.scale_factor, add_offset=packed.add_offset, _FillValue=packed.fill_value)
+            ds[name].encoding.update(enc)
         path = os.path.join(outdir, f"topo_{name}.nc")
         ds.to_netcdf(path)
     else:
         if crop is not None:
             raise NotImplementedError("crop needs xarray coordinates")
-        path = os.path.join(outdir, f"topo_{name}.npy")
-        np.save(path, array)
+        if packed:
+            path = os.path.join(outdir, f"topo_{name}.npz")
+            np.savez(path, values=packed.values, scale_factor=packed.scale_factor, add_offset=packed.add_offset,
+                     fill_value=np.nan if packed.fill_value is None else packed.fill_value)
+        else:
+            path = os.path.join(outdir, f"topo_{name}.npy")
+            np.save(path, array)
     logger.info("saved: %s", path)
     return path
 
@@ -102,15 +115,34 @@ class _ResidentDem:
         self.dev.free()
 
 
+def _leave(plane, packing, row0=0, rows=None):
+    """A device-resident result plane on the host: float32, or packed on the GPU (``DeviceArray.to_packed``)."""
+    return plane.to_host(row0, rows) if packing is None else plane.to_packed(packing, row0, rows)
+
+
 def _finish(array, ind_nans, dem_ds, name, crop, outdir, units, results):
     if ind_nans is not None and len(ind_nans):
-        array[ind_nans] = np.nan
+        if isinstance(array, _lib.PackedPlane):
+            # the fill code (NaN for a float plane) where the caller wants NaN; those that were not missing yet are counted
+            codes = array.values
+            was = codes[ind_nans]
+            if codes.dtype.kind == "f":
+                fill, already = np.nan, np.isnan(was)
+            else:
+                fill, already = codes.dtype.type(array.fill_value), was == array.fill_value
+            codes[ind_nans] = fill
+            array.missing += int(was.size - np.count_nonzero(already))
+        else:
+            array[ind_nans] = np.nan
     write_output(array, dem_ds, name, crop, outdir, units)
     results[name] = array
 
 
-def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir="."):
-    """Gaussian-smoothed DEM per scale, sigma = scale_px / CFG.scale_std (reference topo.py:16-59)."""
+def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir=".", pack=None):
+    """Gaussian-smoothed DEM per scale, sigma = scale_px / CFG.scale_std (reference topo.py:16-59).  ``pack`` (here and in the
+    other wrappers): a ``Packing`` - every plane is encoded on the GPU, leaves it at 1 or 2 bytes a sample, and is returned
+    and saved as a ``PackedPlane`` (``write_output``); ``ind_nans`` then receive the fill code."""
+    packing, = _lib.pack_list(pack, ["dem"])
     hlp.check_dem(dem_ds)
     scales = _as_list(scales)
     scales_pxl, _ = hlp.scale_to_pixel(scales, dem_ds)
@@ -120,15 +152,16 @@ def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir="."):
         for scale, px in zip(scales, scales_pxl):
             sigma = px / CFG.scale_std
             res.block.gaussian(sigma, sigma, out)
-            _finish(out.to_host(), ind_nans, dem_ds, _dem_name(scale), crop, outdir, "m", results)
+            _finish(_leave(out, packing), ind_nans, dem_ds, _dem_name(scale), crop, outdir, "m", results)
     finally:
         out.free()
         res.close()
     return results
 
 
-def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want):
+def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=None):
     hlp.check_dem(dem_ds)
+    packing, = _lib.pack_list(pack, [want])
     scales = _as_list(scales)
     smth_factors = _as_list(smth_factors, len(scales))
     scales_pxl, _ = hlp.scale_to_pixel(scales, dem_ds)
@@ -161,8 +194,8 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want):
                 kb = partner[k]
                 second = second or res.plane()
                 res.block.tpi_multi([int(px), int(scales_pxl[kb])], [out, second])
-                ahead[kb] = second.to_host()
-                _finish(out.to_host(), ind_nans, dem_ds, _tpi_name(scale, fact), crop, outdir, "m", results)
+                ahead[kb] = _leave(second, packing)
+                _finish(_leave(out, packing), ind_nans, dem_ds, _tpi_name(scale, fact), crop, outdir, "m", results)
                 continue
             block = res.block
             if sigma:  # pre-smoothing (reference topo.py:172-173, :297-298)
@@ -171,10 +204,11 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want):
                 block = d.Block(smooth)
             if want == "tpi":
                 block.tpi_std(int(px), tpi=out)
-                array, name = out.to_host(), _tpi_name(scale, fact)
+                array, name = _leave(out, packing), _tpi_name(scale, fact)
             else:
                 block.tpi_std(int(px), std=out)
-                array, name = out.to_host().astype(np.float64), _std_name(scale, fact)
+                array = out.to_host().astype(np.float64) if packing is None else _leave(out, packing)  # (packed: not widened)
+                name = _std_name(scale, fact)
             _finish(array, ind_nans, dem_ds, name, crop, outdir, "m", results)
     finally:
         out.free()
@@ -185,21 +219,24 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want):
     return results
 
 
-def compute_tpi(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir="."):
-    """TPI for every scale (reference topo.py:88-141)."""
+def compute_tpi(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None):
+    """TPI for every scale (reference topo.py:88-141).  ``pack``: see :func:`compute_dem`."""
     logger.info("***Starting TPI computation for scales %s meters***", scales)
-    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "tpi")
+    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "tpi", pack)
 
 
-def compute_std(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir="."):
-    """Windowed standard deviation for every scale (reference topo.py:216-269)."""
+def compute_std(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None):
+    """Windowed standard deviation for every scale (reference topo.py:216-269).  ``pack``: see :func:`compute_dem`; a packed
+    plane is not widened to float64."""
     logger.info("***Starting STD computation for scales %s meters***", scales)
-    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "std")
+    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "std", pack)
 
 
-def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdir="."):
-    """dx, dy, slope, aspect for every scale (reference topo.py:534-594)."""
+def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdir=".", pack=None):
+    """dx, dy, slope, aspect for every scale (reference topo.py:534-594).  ``pack``: a dict with the keys ``dx``, ``dy``,
+    ``slope``, ``aspect`` (a missing key: float32), or one ``Packing`` for the four."""
     hlp.check_dem(dem_ds)
+    packs = _lib.pack_list(pack, topo.GRADIENT_PLANES)
     logger.info("***Starting gradients computation for scales %s meters***", scales)
     scales = _as_list(scales)
     sig_ratios = _as_list(sig_ratios, len(scales))
@@ -214,11 +251,11 @@ def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdi
         for scale, sigma, ratio in zip(scales, sigmas, sig_ratios):
             names = _gradient_names(scale, ratio)
             if two_d:  # per-pixel resolutions (WGS84 grids): host-buffer entry point
-                arrays = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio)
+                arrays = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio, pack=None if pack is None else packs)
             else:
                 res.block.gradient(sigma, res_meters["x"], res_meters["y"], sig_ratio=ratio,
                                    dx=outs[0], dy=outs[1], slope=outs[2], aspect=outs[3])
-                arrays = [o.to_host() for o in outs]
+                arrays = [_leave(o, q) for o, q in zip(outs, packs)]
             for array, name, units in zip(arrays, names, ["1", "1", "degree", "degree"]):
                 _finish(array, ind_nans, dem_ds, name, crop, outdir, units, results)
     finally:
@@ -230,20 +267,20 @@ def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdi
 
 
 def compute_sx(dem_ds, azimuth, radius, height=10.0, azimuth_arc=10.0, azimuth_steps=15,
-               radius_min=0.0, crop=None, outdir="."):
+               radius_min=0.0, crop=None, outdir=".", pack=None):
     """Sx for one azimuth (reference topo.py:715-772).  ``azimuth`` may also be a sequence: the
     planes of all azimuths then come from one pass over the DEM (``topo.sx_multi``), each saved
-    under the name the reference gives it."""
+    under the name the reference gives it.  ``pack``: see :func:`compute_dem`."""
     hlp.check_dem(dem_ds)
     logger.info("***Starting Sx computation for azimuth %s meters and radius %s***", azimuth, radius)
     results = {}
     if np.ndim(azimuth) == 0:
         array = topo.sx(dem_ds, azimuth, radius, height=height, azimuth_arc=azimuth_arc,
-                        azimuth_steps=azimuth_steps, radius_min=radius_min)
+                        azimuth_steps=azimuth_steps, radius_min=radius_min, pack=pack)
         _finish(array, None, dem_ds, _sx_name(radius, azimuth), crop, outdir, "degree", results)
         return results
     arrays = topo.sx_multi(dem_ds, azimuth, radius, height=height, azimuth_arc=azimuth_arc,
-                           azimuth_steps=azimuth_steps, radius_min=radius_min)
+                           azimuth_steps=azimuth_steps, radius_min=radius_min, pack=pack)
     for az, array in zip(azimuth, arrays):
         _finish(array, None, dem_ds, _sx_name(radius, az), crop, outdir, "degree", results)
     return results

@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "decode.hpp"
+#include "encode.hpp"
 
 #include <sys/mman.h>
 
@@ -626,7 +627,15 @@ int download(void* host, const void* dev, size_t bytes) {
 struct HostPlane {
     void* host;
     void* dev;
-    size_t elem = sizeof(float);  // bytes per sample (the missing mask of topo_amd_fill_na_f32: 1)
+    size_t elem = sizeof(float);  // bytes per sample (the missing mask of topo_amd_fill_na_f32: 1; a packed plane: 1 or 2)
+    // A packed result plane (include/topo_amd.h): the kernels write the float32 device plane `f32`, its rows are encoded
+    // behind them into the packed device plane `dev` - taken from the pool by run_pipelined, behind every plane a float32
+    // call takes - and `dev` is what gets downloaded.  f32 == nullptr: a plane downloaded as the kernels write it.
+    const float* f32 = nullptr;
+    EncodeParams enc;
+    topo_amd_plane* report = nullptr;  // the caller's struct: its counters are written after the last chunk
+    void** pool = nullptr;             // a multi-scale call: where the packed device plane (2 bytes a sample) is kept between its scales
+    bool packed() const { return host != nullptr && f32 != nullptr; }
     void* host_row(int r, int nx) const { return (char*)host + (size_t)r * nx * elem; }
     const void* dev_row(int r, int nx) const { return (const char*)dev + (size_t)r * nx * elem; }
 };
@@ -708,14 +717,89 @@ int raw_plane(HostRun& run, const Source& s, int ny, int nx, char** d_raw) {
     return TOPO_AMD_OK;
 }
 
+// A caller's result plane as a host-buffer call sees it: a checked topo_amd_plane (absent: a NULL struct or NULL data, where
+// the call allows it).  Float32 planes are downloaded as the kernels write them, the others encoded first (HostPlane).
+struct OutPlane {
+    void* host = nullptr;
+    EncodeParams enc;
+    topo_amd_plane* report = nullptr;
+    explicit operator bool() const { return host != nullptr; }
+    size_t bytes(int ny, int nx) const { return (size_t)ny * nx * plane_sample_bytes(enc.dtype); }
+    // ... on the float32 device plane the kernels write; pool: see HostPlane
+    HostPlane on(float* dev, void** pool = nullptr) const {
+        HostPlane h{dev ? host : nullptr, dev};
+        if (h.host && !enc.plain()) {
+            h.dev = nullptr;
+            h.elem = plane_sample_bytes(enc.dtype);
+            h.f32 = dev;
+            h.enc = enc;
+            h.report = report;
+            h.pool = pool;
+        }
+        return h;
+    }
+};
+int make_out(topo_amd_plane* plane, const char* who, OutPlane* o) {
+    *o = OutPlane();
+    if (!plane || !plane->data) return TOPO_AMD_OK;
+    TOPO_TRY(make_encode(plane, who, &o->enc));
+    plane->missing = plane->saturated = 0;
+    o->host = plane->data;
+    o->report = plane;
+    return TOPO_AMD_OK;
+}
+topo_amd_plane f32_plane(float* p) { return topo_amd_plane{p, TOPO_AMD_F32, 0, 1.0, 0.0, 0.0, 0, 0}; }
+
 // src: the caller's raster (ignored when upload == false).  A source that is not float32-as-stored goes chunk by chunk into
 // a raw device plane and is decoded into d_in on the stream of the copy, in front of the event the kernels wait for.
 template <class Compute>
 int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, int above, int below, bool upload,
-                  const std::vector<HostPlane>& outs, Compute&& compute) {
+                  std::vector<HostPlane> outs, Compute&& compute) {
     Context& c = ctx();
     char* d_raw = nullptr;
     if (upload) TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    // packed result planes: their device planes (behind every plane a float32 call takes), one pair of counters each
+    unsigned long long* d_counts = nullptr;
+    bool any_packed = false;
+    for (HostPlane& o : outs) {
+        if (!o.packed()) continue;
+        any_packed = true;
+        if (o.pool && *o.pool) {
+            o.dev = *o.pool;
+        } else {
+            TOPO_TRY(run.alloc(&o.dev, (size_t)ny * nx * (o.pool ? 2 : o.elem)));
+            if (o.pool) *o.pool = o.dev;
+        }
+    }
+    if (any_packed) {
+        void* w = nullptr;
+        TOPO_TRY(workspace(kEncodeCountsSlot, outs.size() * 2 * sizeof(unsigned long long), &w));
+        d_counts = (unsigned long long*)w;
+        TOPO_HIP(hipMemsetAsync(d_counts, 0, outs.size() * 2 * sizeof(unsigned long long), c.compute));
+    }
+    // rows [r0, r1) of every packed plane: float32 -> codes, on the compute stream behind the kernels that wrote them
+    auto encode_rows = [&](int r0, int r1) -> int {
+        for (size_t q = 0; q < outs.size(); ++q) {
+            const HostPlane& o = outs[q];
+            if (!o.packed()) continue;
+            TOPO_TRY(launch_encode(c.compute, o.f32 + (size_t)r0 * nx, (size_t)(r1 - r0) * nx, o.enc, (char*)o.dev + (size_t)r0 * nx * o.elem,
+                                   d_counts + 2 * q));
+        }
+        return TOPO_AMD_OK;
+    };
+    // after the last chunk (the compute stream has drained): the counters into the callers' structs
+    auto report_counts = [&]() -> int {
+        if (!any_packed) return TOPO_AMD_OK;
+        std::vector<unsigned long long> counts(outs.size() * 2);
+        TOPO_HIP(hipMemcpyAsync(counts.data(), d_counts, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.compute));
+        TOPO_HIP(hipStreamSynchronize(c.compute));
+        for (size_t q = 0; q < outs.size(); ++q)
+            if (outs[q].packed() && outs[q].report) {
+                outs[q].report->missing = counts[2 * q];
+                outs[q].report->saturated = counts[2 * q + 1];
+            }
+        return TOPO_AMD_OK;
+    };
     const int chunk = pipeline_chunk_rows(ny, nx);
     const std::vector<int> cut = chunk >= ny ? std::vector<int>{0, ny} : pipeline_cuts(ny, chunk);
     const int nchunks = (int)cut.size() - 1;
@@ -725,9 +809,11 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
         if (upload) TOPO_HIP(enqueue_rows(src, d_raw, d_in, 0, ny, nx, c.compute));
         const int rc = compute(ny, 0, ny);
         if (rc != TOPO_AMD_OK && rc != TOPO_AMD_EEMPTY) return rc;
+        TOPO_TRY(encode_rows(0, ny));
         run.ready();
         for (const HostPlane& o : outs) TOPO_TRY(download(o.host, o.dev, (size_t)ny * nx * o.elem));
         TOPO_HIP(hipStreamSynchronize(c.compute));
+        TOPO_TRY(report_counts());
         return rc;
     }
     if (!c.up) {
@@ -828,6 +914,10 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
                 break;
             }
             if (r == TOPO_AMD_EEMPTY) empty = true;  // (Sx: every plane was written; reported at the end)
+            if (const int e = encode_rows(r0, r1); e != TOPO_AMD_OK) {
+                fail(e);
+                break;
+            }
             if (hipEventRecord(computed[next], c.compute) != hipSuccess) {
                 set_error("hipEventRecord(computed chunk) failed");
                 fail(TOPO_AMD_EHIP);
@@ -865,6 +955,7 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
         set_error("%s", down_error.c_str());
         return down_rc;
     }
+    TOPO_TRY(report_counts());
     return empty ? TOPO_AMD_EEMPTY : TOPO_AMD_OK;
 }
 
@@ -1602,13 +1693,16 @@ int topo_amd_fill_na_dev(const float* in, int in_rows, int in_row0, int gny, int
 }
 
 // ---- host-buffer entry points ----------------------------------------------------------------
-int topo_amd_tpi_std_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* tpi_out,
-                         float* std_out) {
+int topo_amd_tpi_std_packed(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, topo_amd_plane* tpi_plane,
+                            topo_amd_plane* std_plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "tpi_std", &src));
     TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std: bad DEM");
+    OutPlane tpi_out, std_out;
+    TOPO_TRY(make_out(tpi_plane, "tpi_std", &tpi_out));
+    TOPO_TRY(make_out(std_plane, "tpi_std", &std_out));
     TOPO_REQUIRE(tpi_out || std_out, "tpi_std: both outputs are NULL");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
     ClassScope cls(scan_source(src, ny, nx));  // the raster class from the caller's array: no launch, no synchronisation
@@ -1619,27 +1713,32 @@ int topo_amd_tpi_std_raw(const topo_amd_raster* raster, int ny, int nx, int size
     TOPO_TRY(run.alloc(&d_in, bytes));
     if (tpi_out) TOPO_TRY(run.alloc(&d_tpi, bytes));
     if (std_out) TOPO_TRY(run.alloc(&d_std, bytes));
-    run.prefault(tpi_out, bytes);
-    run.prefault(std_out, bytes);
-    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {{tpi_out, (float*)d_tpi}, {std_out, (float*)d_std}},
+    run.prefault(tpi_out.host, tpi_out.bytes(ny, nx));
+    run.prefault(std_out.host, std_out.bytes(ny, nx));
+    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {tpi_out.on((float*)d_tpi), std_out.on((float*)d_std)},
                          [&](int view_rows, int r0, int rows) {
                              Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
                              return tpi_std_block(b, size, sigma, shift((float*)d_tpi, r0, nx), shift((float*)d_std, r0, nx));
                          });
 }
 
-int topo_amd_tpi_std_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_scales, const int32_t* sizes,
-                               const double* sigmas, float* const* tpi_outs, float* const* std_outs) {
+int topo_amd_tpi_std_multi_packed(const topo_amd_raster* raster, int ny, int nx, int n_scales, const int32_t* sizes,
+                                  const double* sigmas, topo_amd_plane* tpi_planes, topo_amd_plane* std_planes) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "tpi_std_multi", &src));
     TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std_multi: bad DEM");
     TOPO_REQUIRE(n_scales >= 1 && sizes, "tpi_std_multi: no scales");
-    TOPO_REQUIRE(tpi_outs || std_outs, "tpi_std_multi: both output lists are NULL");
+    TOPO_REQUIRE(tpi_planes || std_planes, "tpi_std_multi: both output lists are NULL");
+    std::vector<OutPlane> tpi_outs(n_scales), std_outs(n_scales);
+    for (int k = 0; k < n_scales; ++k) {
+        TOPO_TRY(make_out(tpi_planes ? tpi_planes + k : nullptr, "tpi_std_multi", &tpi_outs[k]));
+        TOPO_TRY(make_out(std_planes ? std_planes + k : nullptr, "tpi_std_multi", &std_outs[k]));
+    }
     bool any_tpi = false, any_std = false;
     for (int k = 0; k < n_scales; ++k) {
-        const bool t = tpi_outs && tpi_outs[k], s = std_outs && std_outs[k];
+        const bool t = (bool)tpi_outs[k], s = (bool)std_outs[k];
         TOPO_REQUIRE(t || s, "tpi_std_multi: scale %d has no output plane", k);
         any_tpi |= t;
         any_std |= s;
@@ -1652,23 +1751,40 @@ int topo_amd_tpi_std_multi_raw(const topo_amd_raster* raster, int ny, int nx, in
     if (any_tpi) TOPO_TRY(run.alloc(&d_tpi, bytes));
     if (any_std) TOPO_TRY(run.alloc(&d_std, bytes));
     for (int k = 0; k < n_scales; ++k) {
-        if (tpi_outs && tpi_outs[k]) run.prefault(tpi_outs[k], bytes);
-        if (std_outs && std_outs[k]) run.prefault(std_outs[k], bytes);
+        run.prefault(tpi_outs[k].host, tpi_outs[k].bytes(ny, nx));
+        run.prefault(std_outs[k].host, std_outs[k].bytes(ny, nx));
     }
+    void *p_tpi = nullptr, *p_std = nullptr;  // the packed device planes, one of each kind for all the scales
     // scale 0 rides on the upload; every scale overlaps its kernels with its own downloads (the two device planes are
     // reused, so a scale starts when the one before it is down)
     for (int k = 0; k < n_scales; ++k) {
-        float* t = tpi_outs && tpi_outs[k] ? (float*)d_tpi : nullptr;
-        float* sd = std_outs && std_outs[k] ? (float*)d_std : nullptr;
+        float* t = tpi_outs[k] ? (float*)d_tpi : nullptr;
+        float* sd = std_outs[k] ? (float*)d_std : nullptr;
         int above = 0, below = 0;
         TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)sizes[k], sigmas ? sigmas[k] : 0.0, &above, &below));
         TOPO_TRY(run_pipelined(run, src, (float*)d_in, ny, nx, above, below, k == 0,
-                               {{t ? tpi_outs[k] : nullptr, t}, {sd ? std_outs[k] : nullptr, sd}}, [&](int view_rows, int r0, int rows) {
+                               {tpi_outs[k].on(t, &p_tpi), std_outs[k].on(sd, &p_std)}, [&](int view_rows, int r0, int rows) {
                                    Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
                                    return tpi_std_block(b, sizes[k], sigmas ? sigmas[k] : 0.0, shift(t, r0, nx), shift(sd, r0, nx));
                                }));
     }
     return TOPO_AMD_OK;
+}
+
+int topo_amd_tpi_std_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* tpi_out, float* std_out) {
+    topo_amd_plane t = f32_plane(tpi_out), s = f32_plane(std_out);
+    return topo_amd_tpi_std_packed(raster, ny, nx, size, sigma, &t, &s);
+}
+
+int topo_amd_tpi_std_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_scales, const int32_t* sizes,
+                               const double* sigmas, float* const* tpi_outs, float* const* std_outs) {
+    std::vector<topo_amd_plane> t, s;  // (no scales: refused by the callee, behind its other checks)
+    for (int k = 0; k < n_scales; ++k) {
+        if (tpi_outs) t.push_back(f32_plane(tpi_outs[k]));
+        if (std_outs) s.push_back(f32_plane(std_outs[k]));
+    }
+    return topo_amd_tpi_std_multi_packed(raster, ny, nx, n_scales, sizes, sigmas, tpi_outs ? t.data() : nullptr,
+                                         std_outs ? s.data() : nullptr);
 }
 
 int topo_amd_tpi_raw(const topo_amd_raster* raster, int ny, int nx, int size, double sigma, float* out) {
@@ -1684,10 +1800,17 @@ int topo_amd_std_raw(const topo_amd_raster* raster, int ny, int nx, int size, do
 }
 
 int topo_amd_gauss_raw(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, float* out) {
+    topo_amd_plane o = f32_plane(out);
+    return topo_amd_gauss_packed(raster, ny, nx, sigma_y, sigma_x, &o);
+}
+
+int topo_amd_gauss_packed(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, topo_amd_plane* plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "gauss", &src));
+    OutPlane out;
+    TOPO_TRY(make_out(plane, "gauss", &out));
     TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "gauss: bad arguments");
     TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gaussian: negative sigma");
     const size_t bytes = (size_t)ny * nx * sizeof(float);
@@ -1698,8 +1821,8 @@ int topo_amd_gauss_raw(const topo_amd_raster* raster, int ny, int nx, double sig
     void *d_in = nullptr, *d_out = nullptr;
     TOPO_TRY(run.alloc(&d_in, bytes));
     TOPO_TRY(run.alloc(&d_out, bytes));
-    run.prefault(out, bytes);
-    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
+    run.prefault(out.host, out.bytes(ny, nx));
+    return run_pipelined(run, src, (float*)d_in, ny, nx, above, below, true, {out.on((float*)d_out)}, [&](int view_rows, int r0, int rows) {
         return topo_amd_gaussian_dev((const float*)d_in, view_rows, 0, ny, nx, sigma_y, sigma_x, r0, rows, shift((float*)d_out, r0, nx));
     });
 }
@@ -1752,20 +1875,29 @@ int topo_amd_fill_na_raw(const topo_amd_raster* raster, int ny, int nx, const do
 int topo_amd_gradient_raw(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio,
                           int res_mode, const void* res_x, const void* res_y, float* dx_out,
                           float* dy_out, float* slope_out, float* aspect_out) {
+    topo_amd_plane dx = f32_plane(dx_out), dy = f32_plane(dy_out), slope = f32_plane(slope_out), aspect = f32_plane(aspect_out);
+    return topo_amd_gradient_packed(raster, ny, nx, sigma, sig_ratio, res_mode, res_x, res_y, &dx, &dy, &slope, &aspect);
+}
+
+int topo_amd_gradient_packed(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio, int res_mode,
+                             const void* res_x, const void* res_y, topo_amd_plane* dx_out, topo_amd_plane* dy_out,
+                             topo_amd_plane* slope_out, topo_amd_plane* aspect_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "gradient", &src));
     TOPO_REQUIRE(ny >= 1 && nx >= 1, "gradient: bad DEM");
+    topo_amd_plane* planes[4] = {dx_out, dy_out, slope_out, aspect_out};
+    OutPlane host_out[4];
+    for (int k = 0; k < 4; ++k) TOPO_TRY(make_out(planes[k], "gradient", &host_out[k]));
     const size_t bytes = (size_t)ny * nx * sizeof(float);
     ClassScope cls(scan_source(src, ny, nx));
     HostRun run;
     void *d_in = nullptr, *d_o[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* host_out[4] = {dx_out, dy_out, slope_out, aspect_out};
     TOPO_TRY(run.alloc(&d_in, bytes));
     for (int k = 0; k < 4; ++k)
         if (host_out[k]) TOPO_TRY(run.alloc(&d_o[k], bytes));
-    for (int k = 0; k < 4; ++k) run.prefault(host_out[k], bytes);
+    for (int k = 0; k < 4; ++k) run.prefault(host_out[k].host, host_out[k].bytes(ny, nx));
     const void *rx = res_x, *ry = res_y;
     if (res_mode == TOPO_AMD_RES_2D) {
         TOPO_REQUIRE(res_x && res_y, "gradient: resolution arrays are NULL");
@@ -1779,7 +1911,7 @@ int topo_amd_gradient_raw(const topo_amd_raster* raster, int ny, int nx, double 
     }
     const int h = gradient_ghost_rows(sigma, sig_ratio, true);
     std::vector<HostPlane> outs;
-    for (int k = 0; k < 4; ++k) outs.push_back({host_out[k], (float*)d_o[k]});
+    for (int k = 0; k < 4; ++k) outs.push_back(host_out[k].on((float*)d_o[k]));
     return run_pipelined(run, src, (float*)d_in, ny, nx, h, h, true, outs, [&](int view_rows, int r0, int rows) {
         const void *cx = rx, *cy = ry;
         if (res_mode == TOPO_AMD_RES_2D) {  // [out_rows x nx], aligned with the output rows
@@ -1794,10 +1926,18 @@ int topo_amd_gradient_raw(const topo_amd_raster* raster, int ny, int nx, double 
 
 int topo_amd_sx_raw(const topo_amd_raster* raster, int ny, int nx, const int32_t* dj, const int32_t* di,
                     const double* dist, int n_off, int window, double height, float* out) {
+    topo_amd_plane o = f32_plane(out);
+    return topo_amd_sx_packed(raster, ny, nx, dj, di, dist, n_off, window, height, &o);
+}
+
+int topo_amd_sx_packed(const topo_amd_raster* raster, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist,
+                       int n_off, int window, double height, topo_amd_plane* plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "sx", &src));
+    OutPlane out;
+    TOPO_TRY(make_out(plane, "sx", &out));
     TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "sx: bad arguments");
     // (no ray pixel at all: the tables may be NULL; the plane is zero-filled and the call answers TOPO_AMD_EEMPTY, like
     // a sector whose pixels are all NaN)
@@ -1813,8 +1953,8 @@ int topo_amd_sx_raw(const topo_amd_raster* raster, int ny, int nx, const int32_t
     void *d_in = nullptr, *d_out = nullptr;
     TOPO_TRY(run.alloc(&d_in, bytes));
     TOPO_TRY(run.alloc(&d_out, bytes));
-    run.prefault(out, bytes);
-    return run_pipelined(run, src, (float*)d_in, ny, nx, up, down, true, {{out, (float*)d_out}}, [&](int view_rows, int r0, int rows) {
+    run.prefault(out.host, out.bytes(ny, nx));
+    return run_pipelined(run, src, (float*)d_in, ny, nx, up, down, true, {out.on((float*)d_out)}, [&](int view_rows, int r0, int rows) {
         return topo_amd_sx_dev((const float*)d_in, view_rows, 0, ny, nx, dj, di, dist, n_off, window, height, r0, rows,
                                shift((float*)d_out, r0, nx));
     });
@@ -1823,24 +1963,36 @@ int topo_amd_sx_raw(const topo_amd_raster* raster, int ny, int nx, const int32_t
 int topo_amd_sx_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_az, const int32_t* first,
                           const int32_t* dj, const int32_t* di, const double* dist, const int32_t* window,
                           double height, float* const* outs) {
+    std::vector<topo_amd_plane> planes;  // (no planes: refused by the callee, behind its other checks)
+    for (int k = 0; outs && k < n_az; ++k) planes.push_back(f32_plane(outs[k]));
+    return topo_amd_sx_multi_packed(raster, ny, nx, n_az, first, dj, di, dist, window, height, outs && n_az >= 1 ? planes.data() : nullptr);
+}
+
+int topo_amd_sx_multi_packed(const topo_amd_raster* raster, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,
+                             const int32_t* di, const double* dist, const int32_t* window, double height,
+                             topo_amd_plane* out_planes) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
     Source src;
     TOPO_TRY(make_source(raster, "sx_multi", &src));
-    TOPO_REQUIRE(outs && n_az >= 1 && ny >= 1 && nx >= 1, "sx_multi: bad arguments");
+    TOPO_REQUIRE(out_planes && n_az >= 1 && ny >= 1 && nx >= 1, "sx_multi: bad arguments");
     TOPO_REQUIRE(first && dj && di && dist && window, "sx_multi: NULL argument");
-    for (int k = 0; k < n_az; ++k) TOPO_REQUIRE(outs[k], "sx_multi: NULL output plane %d", k);
+    std::vector<OutPlane> outs(n_az);
+    for (int k = 0; k < n_az; ++k) {
+        TOPO_TRY(make_out(out_planes + k, "sx_multi", &outs[k]));
+        TOPO_REQUIRE(outs[k], "sx_multi: NULL output plane %d", k);
+    }
     const size_t bytes = (size_t)ny * nx * sizeof(float);
     HostRun run;
     void* d_in = nullptr;
     std::vector<float*> d_out(n_az, nullptr);
     TOPO_TRY(run.alloc(&d_in, bytes));
     for (int k = 0; k < n_az; ++k) TOPO_TRY(run.alloc((void**)&d_out[k], bytes));
-    for (int k = 0; k < n_az; ++k) run.prefault(outs[k], bytes);
+    for (int k = 0; k < n_az; ++k) run.prefault(outs[k].host, outs[k].bytes(ny, nx));
     int up = 0, down = 0;
     sx_multi_reach(n_az, first, dj, dist, &up, &down);
     std::vector<HostPlane> planes;
-    for (int k = 0; k < n_az; ++k) planes.push_back({outs[k], d_out[k]});
+    for (int k = 0; k < n_az; ++k) planes.push_back(outs[k].on(d_out[k]));
     std::vector<float*> moved(n_az);
     return run_pipelined(run, src, (float*)d_in, ny, nx, up, down, true, planes, [&](int view_rows, int r0, int rows) {
         for (int k = 0; k < n_az; ++k) moved[k] = shift(d_out[k], r0, nx);
@@ -1960,6 +2112,47 @@ int topo_amd_decode_dev(const void* raw_dev, int dtype, size_t count, double sca
         return TOPO_AMD_OK;
     }
     return launch_decode(ctx().compute, raw_dev, dtype, count, src.p, out_dev);
+}
+
+// ---- the encode on its own ---------------------------------------------------------------------------------------------------
+int topo_amd_encode_host(const float* in, size_t count, topo_amd_plane* plane) {
+    EncodeParams p;  // (no GPU, no context: nothing to lock)
+    TOPO_TRY(make_encode(plane, "encode_host", &p));
+    TOPO_REQUIRE((in != nullptr && plane->data != nullptr) || count == 0, "encode_host: NULL array");
+    plane->missing = plane->saturated = 0;
+    if (p.plain()) {
+        if (count) std::memmove(plane->data, in, count * sizeof(float));
+        return TOPO_AMD_OK;
+    }
+    return encode_host_array(in, count, p, plane->data, &plane->missing, &plane->saturated);
+}
+
+int topo_amd_encode_dev(const float* in_dev, size_t count, topo_amd_plane* plane) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    EncodeParams p;
+    TOPO_TRY(make_encode(plane, "encode_dev", &p));
+    TOPO_REQUIRE((in_dev != nullptr && plane->data != nullptr) || count == 0, "encode_dev: NULL array");
+    plane->missing = plane->saturated = 0;
+    if (count == 0) return TOPO_AMD_OK;
+    Context& c = ctx();
+    dem_memo_forget(plane->data, count * plane_sample_bytes(p.dtype));
+    if (p.plain()) {
+        if ((const void*)in_dev != plane->data)
+            TOPO_HIP(hipMemcpyAsync(plane->data, in_dev, count * sizeof(float), hipMemcpyDeviceToDevice, c.compute));
+        TOPO_HIP(hipStreamSynchronize(c.compute));
+        return TOPO_AMD_OK;
+    }
+    void* w = nullptr;
+    TOPO_TRY(workspace(kEncodeCountsSlot, 2 * sizeof(unsigned long long), &w));
+    TOPO_HIP(hipMemsetAsync(w, 0, 2 * sizeof(unsigned long long), c.compute));
+    TOPO_TRY(launch_encode(c.compute, in_dev, count, p, plane->data, (unsigned long long*)w));
+    unsigned long long counts[2] = {0, 0};
+    TOPO_HIP(hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, c.compute));
+    TOPO_HIP(hipStreamSynchronize(c.compute));
+    plane->missing = counts[0];
+    plane->saturated = counts[1];
+    return TOPO_AMD_OK;
 }
 
 int topo_amd_upload_raw(const topo_amd_raster* raster, int ny, int nx, float* out_dev) {

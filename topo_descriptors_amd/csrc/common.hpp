@@ -87,8 +87,9 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
-constexpr int kWorkspaces = 15;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
-                                 // 14: a valley plane group's outputs)
+constexpr int kWorkspaces = 16;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
+                                 // 14: a valley plane group's outputs, 15: the counters of the encode kernel)
+constexpr int kEncodeCountsSlot = 15;
 constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;

@@ -12,13 +12,16 @@ from . import _lib
 
 
 class DeviceArray:
-    """rows x nx plane in HBM owned by libtopo_amd: float32, or uint8 for the missing mask of :meth:`Block.fill_na`."""
+    """rows x nx plane in HBM owned by libtopo_amd: float32, uint8 for the missing mask of :meth:`Block.fill_na`, or the
+    sample types of a packed result plane (int16, uint16, uint8, float16: :meth:`to_packed`)."""
+
+    DTYPES = tuple(np.dtype(t) for t in (np.float32, np.uint8, np.int16, np.uint16, np.float16))
 
     def __init__(self, rows, nx, dtype=np.float32):
         self.rows, self.nx = int(rows), int(nx)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError(f"DeviceArray: float32 or uint8 planes, not {self.dtype}")
+        if self.dtype not in self.DTYPES:
+            raise ValueError(f"DeviceArray: float32, uint8, int16, uint16 or float16 planes, not {self.dtype}")
         self.nbytes = self.rows * self.nx * self.dtype.itemsize
         p = C.c_void_p()
         _lib.check(_lib.lib().topo_amd_malloc(C.byref(p), self.nbytes), "topo_amd_malloc")
@@ -42,6 +45,20 @@ class DeviceArray:
         _lib.check(_lib.lib().topo_amd_memcpy_d2h(_lib.ptr(out), self.row_ptr(row0), out.nbytes),
                    "memcpy_d2h")
         return out
+
+    def to_packed(self, packing, row0=0, rows=None):
+        """Rows of this float32 plane as a ``PackedPlane``: encoded on the GPU into a packed device plane
+        (``topo_amd_encode_dev``), which is what crosses the link.  The twin of :meth:`to_host`."""
+        if self.dtype != np.float32:
+            raise ValueError(f"DeviceArray.to_packed: a float32 plane is encoded, not {self.dtype}")
+        rows = self.rows - row0 if rows is None else rows
+        dev = DeviceArray(rows, self.nx, dtype=packing.dtype)
+        try:
+            plane = packing.struct(dev.ptr)
+            _lib.check(_lib.lib().topo_amd_encode_dev(self.row_ptr(row0), rows * self.nx, C.byref(plane)), "encode_dev")
+            return _lib.PackedPlane(dev.to_host(), packing, plane.missing, plane.saturated)
+        finally:
+            dev.free()
 
     def upload_rows(self, array, row0=0):
         a = np.ascontiguousarray(array, dtype=self.dtype)

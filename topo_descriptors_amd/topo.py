@@ -57,6 +57,20 @@ def _plane(shape):
     return np.empty(shape, dtype=np.float32)
 
 
+def _packed_tpi_std(values, size, sigma, packs, want):
+    """``topo_amd_tpi_std_packed``: the planes of ``want`` (tpi, std) with the packings ``packs``; an unpacked STD plane is
+    widened to float64 as :func:`std` does."""
+    keep, src, shape = _source(values)
+    made = [_lib.result_plane(q, shape) if w else None for q, w in zip(packs, want)]
+    refs = [C.byref(m[1]) if m else None for m in made]
+    _lib.check(_lib.lib().topo_amd_tpi_std_packed(src, shape[0], shape[1], int(size), _sigma_arg(sigma), *refs),
+               "topo_amd_tpi_std_packed")
+    out = [_lib.wrap_plane(*m, q) if m else None for m, q in zip(made, packs)]
+    if want[1] and packs[1] is None:
+        out[1] = out[1].astype(np.float64)
+    return out
+
+
 def _check_2d(a, who):
     if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError(f"{who}: expected a non-empty 2-D array, got shape {a.shape}")
@@ -78,7 +92,7 @@ def circular_kernel(size):
     return mask
 
 
-def tpi(dem, size, sigma=None):
+def tpi(dem, size, sigma=None, pack=None):
     """Topographic position index: elevation minus the mean of the disc neighbourhood of
     diameter ``size`` pixels, centre excluded; optional Gaussian pre-smoothing ``sigma``
     (reference topo.py:145-181).  float32 in, float32 out; DataArray in, DataArray out.
@@ -94,9 +108,14 @@ def tpi(dem, size, sigma=None):
     the mean and TPI (about 0.02 mm rms at 67 pixels when the fractional parts are spread evenly) - the order of the
     1.4 - 1.7 mm the reference's own float32 FFT is off by, and far inside 1e-4 of the range.  Smaller discs, and
     :func:`tpi_std`, are exact to 2**-16 m; ``TOPO_AMD_TPI_FRACTION_EXACT=1`` makes this function so as well, at about
-    twice the time on such a DEM."""
+    twice the time on such a DEM.
+
+    ``pack``: a :class:`Packing` - the plane is encoded on the GPU and comes back as a :class:`PackedPlane` (never re-wrapped
+    into a DataArray), over the link at 1 or 2 bytes a sample; ``None``: float32 as ever."""
     values, rewrap = _unwrap(dem)
     _check_2d(values, "tpi")
+    if pack is not None:
+        return _packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi"]) + [None], (True, False))[0]
     keep, src, shape = _source(values)
     out = _plane(shape)
     lib = _lib.lib()
@@ -105,12 +124,14 @@ def tpi(dem, size, sigma=None):
     return rewrap(out)
 
 
-def std(dem, size, sigma=None):
+def std(dem, size, sigma=None, pack=None):
     """Sample standard deviation inside the disc window, with the reference's int32
     truncation of the squared term (reference topo.py:273-307).  Returns float64.  Non-finite samples: as for
-    :func:`tpi` (and :func:`dem` when ``sigma`` is given)."""
+    :func:`tpi` (and :func:`dem` when ``sigma`` is given).  ``pack``: as for :func:`tpi`; a packed plane is not widened."""
     values, _ = _unwrap(dem)
     _check_2d(values, "std")
+    if pack is not None:
+        return _packed_tpi_std(values, size, sigma, [None] + _lib.pack_list(pack, ["std"]), (False, True))[1]
     keep, src, shape = _source(values)
     out = _plane(shape)
     lib = _lib.lib()
@@ -119,11 +140,14 @@ def std(dem, size, sigma=None):
     return out.astype(np.float64)
 
 
-def tpi_std(dem, size, sigma=None):
+def tpi_std(dem, size, sigma=None, pack=None):
     """TPI and STD of the same window in one pass over the DEM (no reference counterpart:
-    the reference convolves three times for the pair)."""
+    the reference convolves three times for the pair).  ``pack``: one :class:`Packing` for both planes, or a pair / a dict
+    with the keys ``tpi`` and ``std`` (``None``: that plane stays float32, STD widened to float64)."""
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std")
+    if pack is not None:
+        return tuple(_packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi", "std"]), (True, True)))
     keep, src, shape = _source(values)
     t = _plane(shape)
     s = _plane(shape)
@@ -134,11 +158,13 @@ def tpi_std(dem, size, sigma=None):
     return t, s.astype(np.float64)
 
 
-def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
+def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True, pack=None):
     """TPI and / or STD for several disc sizes from one upload of the DEM (the multi-scale half):
     what the reference's ``compute_tpi`` / ``compute_std`` loops do scale by scale (topo.py:88-141, :216-269).
     Returns ``(tpis, stds)``, lists of planes in the order of ``sizes`` (``None`` for the kind not asked
-    for); every plane has the bits of the single call."""
+    for); every plane has the bits of the single call.  ``pack``: one :class:`Packing` for every plane, or a pair / a dict
+    with the keys ``tpi`` and ``std`` whose entries are ``None`` (float32), a :class:`Packing` or a sequence with one entry per
+    size."""
     import ctypes as C
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std_multi")
@@ -150,6 +176,31 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
     else:
         sig = np.array([_sigma_arg(v) for v in np.broadcast_to(np.asarray(sigmas, dtype=object), (n,))],
                        dtype=np.float64)
+    if pack is not None:
+        if isinstance(pack, _lib.Packing):
+            kinds = [pack, pack]
+        else:
+            kinds = [pack.get("tpi"), pack.get("std")] if isinstance(pack, dict) else list(pack)
+        if len(kinds) != 2:
+            raise ValueError("tpi_std_multi: pack is one Packing, or a pair / dict (tpi, std)")
+        names = [str(k) for k in range(n)]
+        lists, arrays = [], []
+        for kind, want in zip(kinds, (want_tpi, want_std)):
+            packs = _lib.pack_list(kind, names)
+            made = [_lib.result_plane(q, shape) for q in packs] if want else None
+            lists.append((packs, made))
+            arrays.append(_lib.plane_array([m[1] for m in made]) if want else None)
+        _lib.check(_lib.lib().topo_amd_tpi_std_multi_packed(src, shape[0], shape[1], n, sizes.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            sig.ctypes.data_as(C.POINTER(C.c_double)), *arrays),
+                   "topo_amd_tpi_std_multi_packed")
+        out = []
+        for (packs, made), structs, widen in zip(lists, arrays, (False, True)):
+            if made is None:
+                out.append(None)
+                continue
+            planes = [_lib.wrap_plane(m[0], structs[k], q) for k, (m, q) in enumerate(zip(made, packs))]
+            out.append([p.astype(np.float64) if widen and q is None else p for p, q in zip(planes, packs)])
+        return tuple(out)
     tpis = [_plane(shape) for _ in range(n)] if want_tpi else None
     stds = [_plane(shape) for _ in range(n)] if want_std else None
 
@@ -168,7 +219,7 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True):
 
 
 # ---- Gaussian, Sobel, gradient ------------------------------------------------------------------
-def dem(dem, sigma):
+def dem(dem, sigma, pack=None):
     """Gaussian-smoothed DEM, reflect boundary, 4-sigma truncation (reference topo.py:62-80).
     ``sigma`` may be a scalar or an (axis0, axis1) pair.
 
@@ -181,11 +232,20 @@ def dem(dem, sigma):
     vector-ALU kernels instead.)  The vector-ALU kernels
     (shorter or much longer filters) pad their taps to chunks of 8 or 16 and spoil up to one chunk more
     towards lower indices.  ``tests/test_gpu_parity.py::test_gaussian_nan_footprint`` pins both.
+
+    ``pack``: as for :func:`tpi`.  The :class:`PackedPlane` it gives is a source like any ``PackedDem``: a smoothed DEM packed
+    to uint16 goes back into :func:`tpi` at 2 bytes a sample each way.
     """
     values, rewrap = _unwrap(dem)
     _check_2d(values, "dem")
     sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (2,))
     keep, src, shape = _source(values)
+    if pack is not None:
+        packing, = _lib.pack_list(pack, ["dem"])
+        out, plane = _lib.result_plane(packing, shape)
+        _lib.check(_lib.lib().topo_amd_gauss_packed(src, shape[0], shape[1], float(sig[0]), float(sig[1]), C.byref(plane)),
+                   "topo_amd_gauss_packed")
+        return _lib.wrap_plane(out, plane, packing)
     out = _plane(shape)
     lib = _lib.lib()
     _lib.check(lib.topo_amd_gauss_raw(src, shape[0], shape[1], float(sig[0]),
@@ -225,18 +285,30 @@ def _resolution_args(res_meters, shape):
     return _lib.RES_2D, rx, ry
 
 
-def gradient(dem, sigma, res_meters, sig_ratio=1):
+GRADIENT_PLANES = ("dx", "dy", "slope", "aspect")
+
+
+def gradient(dem, sigma, res_meters, sig_ratio=1, pack=None):
     """[dx, dy, slope, aspect] of the Gaussian-smoothed DEM (reference topo.py:598-644).
 
     ``sigma <= 1`` uses the Sobel pair; ``sig_ratio != 1`` smooths with ``sigma*sig_ratio``
     perpendicular to each derivative.  Derivatives are divided by the signed grid
     resolution ``res_meters`` (second return of :func:`helpers.scale_to_pixel`); slope in
     degrees; aspect in [0, 360) with north-facing = 0 and east-facing = 90.  Non-finite samples reach as far as in
-    :func:`dem` (plus the one pixel of the finite difference)."""
+    :func:`dem` (plus the one pixel of the finite difference).
+
+    ``pack``: one :class:`Packing` for the four planes, a sequence of four, or a dict with the keys ``dx``, ``dy``, ``slope``,
+    ``aspect`` (``None`` or a missing key: that plane stays float32); packed planes come back as :class:`PackedPlane`."""
     values, _ = _unwrap(dem)
     _check_2d(values, "gradient")
     keep, src, shape = _source(values)
     mode, rx, ry = _resolution_args(res_meters, shape)
+    if pack is not None:
+        packs = _lib.pack_list(pack, GRADIENT_PLANES)
+        made = [_lib.result_plane(q, shape) for q in packs]
+        _lib.check(_lib.lib().topo_amd_gradient_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), mode, _lib.ptr(rx),
+                                                       _lib.ptr(ry), *[C.byref(m[1]) for m in made]), "topo_amd_gradient_packed")
+        return [_lib.wrap_plane(*m, q) for m, q in zip(made, packs)]
     outs = [_plane(shape) for _ in range(4)]
     lib = _lib.lib()
     _lib.check(lib.topo_amd_gradient_raw(src, shape[0], shape[1], float(sigma),
@@ -286,12 +358,18 @@ def _sx_bresenhamlines(start, end):
     return pts[keep]
 
 
-def _sx_scan(dem, reach, rows, cols, metres, height):
+def _sx_scan(dem, reach, rows, cols, metres, height, pack=None):
     """Kernel K6 on a host array: for every pixel the largest elevation angle (degrees) towards the ray pixels
     ``(rows[k], cols[k])`` (offsets from the pixel) at ``metres[k]`` horizontal distance, seen from ``height``
-    above the pixel.  NaN distances are skipped; a frame of ``reach`` pixels stays 0."""
+    above the pixel.  NaN distances are skipped; a frame of ``reach`` pixels stays 0.  ``pack``: a :class:`Packing`; the
+    planes made on the host (nothing but frame, no usable ray pixel) are packed there."""
     dem = _values(dem)
     _check_2d(dem, "_sx_rolling")
+    if pack is not None:
+        packing, = _lib.pack_list(pack, ["sx"])
+        ny, nx = dem.shape
+        if ny <= 2 * reach or nx <= 2 * reach or np.size(metres) == 0 or np.all(np.isnan(metres)):
+            return _lib.encode_host(_sx_scan(np.zeros(dem.shape, np.float32), reach, rows, cols, metres, height), packing)
     metres = np.ascontiguousarray(metres, dtype=np.float64)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
@@ -303,6 +381,12 @@ def _sx_scan(dem, reach, rows, cols, metres, height):
         # nanmax over an empty / all-NaN set: NaN inside the frame, like numpy
         out[reach : ny - reach, reach : nx - reach] = np.nan
         return out.astype(dem.dtype, copy=False)
+    if pack is not None:
+        out, plane = _lib.result_plane(packing, (ny, nx))
+        _lib.check(_lib.lib().topo_amd_sx_packed(src, ny, nx, rows.ctypes.data_as(_lib._i32p), cols.ctypes.data_as(_lib._i32p),
+                                                 metres.ctypes.data_as(_lib._f64p), int(metres.size), int(reach), float(height),
+                                                 C.byref(plane)), "topo_amd_sx_packed")
+        return _lib.wrap_plane(out, plane, packing)
     lib = _lib.lib()
     _lib.check(lib.topo_amd_sx_raw(src, ny, nx, rows.ctypes.data_as(_lib._i32p),
                                    cols.ctypes.data_as(_lib._i32p), metres.ctypes.data_as(_lib._f64p),
@@ -334,26 +418,27 @@ def _sx_sector(azimuth, radius, spacing_x, spacing_y, azimuth_arc=10.0, azimuth_
     return reach, cells[:, 0] - reach, cells[:, 1] - reach, table[cells[:, 0], cells[:, 1]]
 
 
-def sx(dem_ds, azimuth, radius, height=10.0, azimuth_arc=10.0, azimuth_steps=15, radius_min=0.0):
+def sx(dem_ds, azimuth, radius, height=10.0, azimuth_arc=10.0, azimuth_steps=15, radius_min=0.0, pack=None):
     """Sx (Winstral et al.): maximum slope towards the terrain within ``radius`` metres in a
     sector of ``azimuth_arc`` degrees around ``azimuth`` (reference topo.py:776-858).
 
     ``dem_ds`` must be a Dataset (TypeError otherwise, like the reference); the mean signed
     grid spacing is used; pixels closer than ``radius_min`` are ignored; ``height`` is the
-    instrument height added to the target pixel."""
+    instrument height added to the target pixel.  ``pack``: as for :func:`tpi`."""
     if not hlp._looks_like_dataset(dem_ds):
         raise TypeError("Argument 'dem_ds' must be a xr.Dataset.")
     spacing = hlp.scale_to_pixel(radius, dem_ds)[1]
     sector = _sx_sector(azimuth, radius, spacing["x"].mean(), spacing["y"].mean(), azimuth_arc, azimuth_steps,
                         radius_min)
-    return _sx_scan(hlp.get_da(dem_ds).values, *sector, height)
+    return _sx_scan(hlp.get_da(dem_ds).values, *sector, height, pack=pack)
 
 
-def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_steps=15, radius_min=0.0):
+def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_steps=15, radius_min=0.0, pack=None):
     """``sx`` for a sequence of azimuths in one pass over the DEM: ``[sx(dem_ds, a, radius, ...) for a
     in azimuths]`` with the same bits.  The reference scans one azimuth per call (topo.py:776-858) and
     its users loop; here the DEM is uploaded once and ray pixels shared by neighbouring sectors are
-    scanned once.  Give the azimuths in angular order for the sharing to apply."""
+    scanned once.  Give the azimuths in angular order for the sharing to apply.  ``pack``: one
+    :class:`Packing` for every plane or a sequence with one entry per azimuth (``None``: float32)."""
     if not hlp._looks_like_dataset(dem_ds):
         raise TypeError("Argument 'dem_ds' must be a xr.Dataset.")
     azimuths = [float(a) for a in np.atleast_1d(azimuths)]
@@ -367,6 +452,29 @@ def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_st
     dem = _values(hlp.get_da(dem_ds).values)
     _check_2d(dem, "sx_multi")
     keep, src, (ny, nx) = _source(dem)
+    packs = _lib.pack_list(pack, [str(a) for a in azimuths])
+    if pack is not None:
+        outs, structs = [None] * len(sectors), [None] * len(sectors)
+        todo = []
+        for k, (window, _, _, dist) in enumerate(sectors):
+            if ny <= 2 * window or nx <= 2 * window or dist.size == 0 or np.all(np.isnan(dist)):
+                plane = np.zeros((ny, nx), dtype=np.float32)  # made on the host, like below
+                if ny > 2 * window and nx > 2 * window:
+                    plane[window : ny - window, window : nx - window] = np.nan
+                outs[k] = plane if packs[k] is None else _lib.encode_host(plane, packs[k])
+                continue
+            outs[k], structs[k] = _lib.result_plane(packs[k], (ny, nx))
+            todo.append(k)
+        if todo:
+            first, dj, di, dist, window = device.pack_sectors([sectors[k] for k in todo])
+            planes = _lib.plane_array([structs[k] for k in todo])
+            _lib.check(_lib.lib().topo_amd_sx_multi_packed(
+                src, ny, nx, len(todo), first.ctypes.data_as(_lib._i32p), dj.ctypes.data_as(_lib._i32p),
+                di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
+                float(height), planes), "topo_amd_sx_multi_packed")
+            for n, k in enumerate(todo):
+                outs[k] = _lib.wrap_plane(outs[k], planes[n], packs[k])
+        return [o if isinstance(o, _lib.PackedPlane) else o.astype(dem.dtype, copy=False) for o in outs]
     outs = [np.zeros((ny, nx), dtype=np.float32) for _ in sectors]
     # sectors the device has something to do for: the DEM is larger than the zero frame and there
     # is a usable ray pixel (else zeros, or NaN inside the frame, as in _sx_rolling)
