@@ -348,6 +348,26 @@ int topo_amd_disc_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
 int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* stdev);
+/* The same two numbers with the BITS numpy's own float32 a.mean() / a.std() give for a C-contiguous float32 array of count
+ * samples (csrc/moments_np.hip) - what the reference standardises the DEM with (topo.py:427); near-tied directions of the
+ * valley / ridge index flip on their last digit, so the float64 moments above are not a substitute.  numpy's order: chunks
+ * of `chunk` samples (np.getbufsize(); 8192 by default) each reduced by its pairwise sum (leaves of 128 samples on eight
+ * accumulators, neighbours combined level by level), the chunk sums added one after the other from 0.0f, a partial last
+ * chunk the same way; mean = sum / (float)count; std = sqrtf(sum((a - mean) * (a - mean)) / (float)count), the difference
+ * and the product each rounded to float32, summed in that order.  The sums of the full chunks are formed on the GPU, the
+ * chain over them and the tail on the host; the call returns when both numbers are there.  chunk: a power of two >= 128,
+ * anything else is TOPO_AMD_EINVAL; count >= 1.  Non-finite samples give what IEEE arithmetic gives in that order (a NaN
+ * result is a NaN; its payload is not specified).                                                                       */
+int topo_amd_mean_std_f32_dev(const float* in, size_t count, size_t chunk, float* mean, float* stdev);
+/* topo_amd_valley_ridge_dev on a device block that is the WHOLE raster [ny x nx], standardised with the moments
+ * topo_amd_mean_std_f32_dev forms of it; moments_out (may be NULL): {mean, std}.                                        */
+int topo_amd_valley_ridge_std_dev(const float* in, int ny, int nx, const float* taps, const int32_t* ksize,
+                                  const float* angles, int n_angles, int n_planes, size_t chunk, float* norm_out,
+                                  float* dir_out, float moments_out[2]);
+/* What the calling thread's last valley / ridge call did about the moments (for tests and diagnostics): 0 taken from the
+ * caller (topo_amd_valley_ridge_dev / _f32 / _raw), 1 formed on the device in numpy's order (topo_amd_valley_ridge_std_dev
+ * / _std_raw / _packed), 2 the float64 all-reduce of a sharded call.  topo_amd_valley_route is not touched by this.      */
+int topo_amd_valley_moments_route(int* route);
 
 /* Gaps of a DEM filled with the nearest valid sample along x: replaces hlp.fill_na(dem_ds) (reference helpers.py:137-154,
  * interpolate_na(dim="x", method="nearest", fill_value="extrapolate")) together with the masking at or below
@@ -469,6 +489,14 @@ int topo_amd_sx_multi_raw(const topo_amd_raster* src, int ny, int nx, int n_az, 
 int topo_amd_valley_ridge_raw(const topo_amd_raster* src, int ny, int nx, const float* taps, const int32_t* ksize,
                               const float* angles, int n_angles, int n_planes, double mean, double stdev, float* norm_out,
                               float* dir_out);
+/* The standardised index of a host raster in one call: `src` is uploaded and decoded once, smoothed on the device when
+ * sigma > 0 (the kernels topo_amd_gauss_raw runs on it: the bits of that call), the moments of that field are taken by
+ * topo_amd_mean_std_f32_dev (chunk: see there) and written to moments_out (may be NULL), and the index of
+ * topo_amd_valley_ridge_dev is downloaded.  Bit for bit topo_amd_valley_ridge_raw of the (smoothed) float32 array with
+ * numpy's float32 mean() / std() of it.  One chunk, like topo_amd_valley_ridge_raw.                                      */
+int topo_amd_valley_ridge_std_raw(const topo_amd_raster* src, int ny, int nx, const float* taps, const int32_t* ksize,
+                                  const float* angles, int n_angles, int n_planes, double sigma, size_t chunk,
+                                  float* norm_out, float* dir_out, float moments_out[2]);
 
 /* ---- packed result planes: a result encoded on the GPU, downloaded as the file will store it -----------------------------
  * The users' files hold these quantities packed - CF scale_factor / add_offset / _FillValue in netCDF, int16 in GeoTIFF -
@@ -491,8 +519,9 @@ int topo_amd_valley_ridge_raw(const topo_amd_raster* src, int ny, int nx, const 
  * TOPO_AMD_F32: scale 1, offset 0, no nodata; the plane is passed through - no encode runs, no extra device plane is
  * taken, both counters are 0.  The *_raw entry points are the *_packed ones called with such planes.
  * Anything else (I32, F64, an unknown dtype, a nodata inside the range) is TOPO_AMD_EINVAL.
- * Sobel, fill_na and the valley / ridge index stay float32-only: topo_amd_valley_ridge_* is one chunk by design and its
- * planes are small next to its run time.  Row shards encode their device planes with topo_amd_encode_dev.                */
+ * Sobel and fill_na stay float32-only.  The valley / ridge index is packed by topo_amd_valley_ridge_packed (one chunk by
+ * design: both planes are encoded behind the index and then downloaded); its direction plane holds whole degrees
+ * 0 ... 179, which uint8 with scale 1 stores exactly.  Row shards encode their device planes with topo_amd_encode_dev.   */
 #define TOPO_AMD_F16 6
 typedef struct topo_amd_plane {
     void* data;         /* host, ny x nx samples of dtype, C-contiguous; NULL where the _raw namesake allows NULL */
@@ -525,6 +554,10 @@ int topo_amd_sx_packed(const topo_amd_raster* src, int ny, int nx, const int32_t
 int topo_amd_sx_multi_packed(const topo_amd_raster* src, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,
                              const int32_t* di, const double* dist, const int32_t* window, double height,
                              topo_amd_plane* outs);
+/* topo_amd_valley_ridge_std_raw (above) with packed result planes; both planes are required.                            */
+int topo_amd_valley_ridge_packed(const topo_amd_raster* src, int ny, int nx, const float* taps, const int32_t* ksize,
+                                 const float* angles, int n_angles, int n_planes, double sigma, size_t chunk,
+                                 topo_amd_plane* norm_out, topo_amd_plane* dir_out, float moments_out[2]);
 
 /* ---- row sharding over the GPUs of one node (RCCL over xGMI) -------------------------- */
 /* The reference's only precedent is dask map_overlap(depth, boundary="none") for TPI

@@ -59,6 +59,7 @@ SIGNATURES = {
     "topo_amd_release_host_planes": (C.c_int, []),
     "topo_amd_host_chunks": (C.c_int, [_i32p]),
     "topo_amd_valley_route": (C.c_int, [_i32p]),
+    "topo_amd_valley_moments_route": (C.c_int, [_i32p]),
     "topo_amd_tpi_route": (C.c_int, [_i32p]),
     "topo_amd_sx_route": (C.c_int, [_i32p]),
     "topo_amd_gradient_route": (C.c_int, [_i32p]),
@@ -97,6 +98,9 @@ SIGNATURES = {
     "topo_amd_valley_ridge_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int,
                                             C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp]),
     "topo_amd_mean_std_dev": (C.c_int, [_vp, C.c_size_t, _f64p, _f64p]),
+    "topo_amd_mean_std_f32_dev": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _f32p, _f32p]),
+    "topo_amd_valley_ridge_std_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp,
+                                                _f32p]),
     "topo_amd_fill_na_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_double, C.c_int, C.c_int,
                                        _vp, _vp]),
     "topo_amd_valley_ridge_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int,
@@ -119,6 +123,8 @@ SIGNATURES = {
     "topo_amd_upload_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp]),
     "topo_amd_valley_ridge_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int,
                                             C.c_double, C.c_double, _vp, _vp]),
+    "topo_amd_valley_ridge_std_raw": (C.c_int, [_rp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int, C.c_double,
+                                                C.c_size_t, _vp, _vp, _f32p]),
     "topo_amd_tpi_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
     "topo_amd_std_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
     "topo_amd_tpi_std_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp]),
@@ -143,6 +149,8 @@ SIGNATURES = {
                                      C.c_double, _pp]),
     "topo_amd_sx_multi_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _i32p,
                                            C.c_double, _pp]),
+    "topo_amd_valley_ridge_packed": (C.c_int, [_rp, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int, C.c_double,
+                                               C.c_size_t, _pp, _pp, _f32p]),
     "topo_amd_shard_sx_multi": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
                                           _i32p, _f64p, _i32p, C.c_double, C.POINTER(_vp)]),
     "topo_amd_shard_valley_ridge": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int,

@@ -102,8 +102,7 @@ class _ResidentDem:
 
     @property
     def host(self):
-        """The float32 array on the host, made when somebody asks (the un-smoothed valley / ridge index: numpy's mean and
-        std): the plane the GPU decoded."""
+        """The float32 array on the host, made when somebody asks: the plane the GPU decoded."""
         if self._host is None:
             self._host = self.dev.to_host()
         return self._host
@@ -287,12 +286,14 @@ def compute_sx(dem_ds, azimuth, radius, height=10.0, azimuth_arc=10.0, azimuth_s
 
 
 def compute_valley_ridge(dem_ds, scales, mode, flat_list=[0, 0.15, 0.3], smth_factors=None, ind_nans=(),  # noqa: B006
-                         crop=None, outdir="."):
+                         crop=None, outdir=".", pack=None):
     """Valley or ridge index (norm and direction) for every scale (reference topo.py:317-386).
 
-    The DEM goes to the GPU once; per scale the optional pre-smoothing and the 180-angle pass run on the
-    device-resident plane (the mean and standard deviation are numpy's, see below)."""
+    The DEM goes to the GPU once; per scale the optional pre-smoothing, numpy's float32 mean and standard deviation of the
+    (smoothed) plane and the 180-angle pass run on the device-resident plane, and only the two result planes leave it.
+    ``pack``: one ``Packing`` for both planes, or a dict with the keys ``norm`` and ``direction``."""
     hlp.check_dem(dem_ds)
+    packs = _lib.pack_list(pack, ["norm", "direction"])
     if mode not in ("valley", "ridge"):
         raise ValueError(f"Unknown mode {mode!r}")
     logger.info("***Starting %s index computation for scales %s meters***", mode, scales)
@@ -315,21 +316,19 @@ def compute_valley_ridge(dem_ds, scales, mode, flat_list=[0, 0.15, 0.3], smth_fa
         ahead = pool.submit(tables, scales_pxl[0]) if len(scales) else None
         for k, (scale, px, fact, sigma) in enumerate(zip(scales, scales_pxl, smth_factors, sigmas)):
             logger.info("Computing scale %s meters with smoothing factor %s ...", scale, fact)
-            block, plane = res.block, res.dev
+            block = res.block
             if sigma:  # pre-smoothing (reference topo.py:424-425)
                 smooth = smooth or res.plane()
                 res.block.gaussian(sigma, sigma, smooth)
-                block, plane = d.Block(smooth), smooth
-            # numpy's own float32 mean / std of the whole (smoothed) array, like the reference (topo.py:427)
-            # and like topo.valley_ridge: the wrapper and the single call then agree bit for bit, also where
-            # two directions nearly tie
-            field = plane.to_host() if sigma else res.host
-            mean, stdev = float(field.mean()), float(field.std())
+                block = d.Block(smooth)
             n_planes, taps, ksize, ang = ahead.result()
             ahead = pool.submit(tables, scales_pxl[k + 1]) if k + 1 < len(scales) else None
-            block.valley_ridge(taps, ksize, ang, n_planes, mean, stdev, norm, direction)
-            for array, name in zip((norm.to_host(), direction.to_host()), _valley_ridge_names(scale, mode, fact)):
-                _finish(array, ind_nans, dem_ds, name, crop, outdir, "1", results)
+            # numpy's own float32 mean / std of the whole (smoothed) array, like the reference (topo.py:427) and like
+            # topo.valley_ridge - the wrapper and the single call agree bit for bit, also where two directions nearly tie -
+            # formed on the resident plane (device.mean_std_numpy): the block is the whole raster
+            block.valley_ridge(taps, ksize, ang, n_planes, norm=norm, direction=direction)
+            for plane, packing, name in zip((norm, direction), packs, _valley_ridge_names(scale, mode, fact)):
+                _finish(_leave(plane, packing), ind_nans, dem_ds, name, crop, outdir, "1", results)
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
         for a in (norm, direction, smooth):

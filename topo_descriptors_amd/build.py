@@ -13,6 +13,7 @@ NGROUPS = 16  # the per-size disc kernels: one source (disc_wave_group.hip), com
 UNITS = [("sx.hip", [], "sx.o"), ("gauss.hip", [], "gauss.o")] + \
         [("disc_wave_group.hip", [f"-DTOPO_GROUP={g}", f"-DTOPO_NGROUPS={NGROUPS}"], f"disc_wave_group{g}.o") for g in range(NGROUPS)] + \
         [(s, [], s.replace(".hip", ".o")) for s in ("disc_pair.hip", "disc.hip", "disc_wave.hip", "disc_big.hip", "valley.hip",
+                                                    "moments_np.hip",
                                                     "valley_mfma.hip", "valley_fft.hip", "fill.hip", "decode.hip", "encode.hip",
                                                     "capi.hip")]
 SOURCES = sorted({u[0] for u in UNITS})

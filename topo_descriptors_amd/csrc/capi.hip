@@ -532,6 +532,7 @@ int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float*
 // while the upload and the kernels run; ready() joins them before the first download.
 thread_local int t_tpi_route = 0;     // 1: the calling thread's last TPI / STD disc call took the wide ring (topo_amd_tpi_route)
 thread_local int t_valley_route = 0;  // the evaluation the calling thread's last valley / ridge call took (topo_amd_valley_route)
+thread_local int t_valley_moments = 0;  // 1: that call formed the DEM's mean / std on the device (topo_amd_valley_moments_route)
 thread_local int t_sx_route = 0;      // the kernel route the calling thread's last Sx call took (topo_amd_sx_route)
 thread_local int t_gradient_route = 0;  // the same of its last gradient call (topo_amd_gradient_route)
 thread_local int t_disc_route = 0;      // the same of its last TPI / STD disc call (topo_amd_disc_route)
@@ -1192,6 +1193,12 @@ int topo_amd_valley_route(int* route) {
     return TOPO_AMD_OK;
 }
 
+int topo_amd_valley_moments_route(int* route) {
+    TOPO_REQUIRE(route != nullptr, "valley_moments_route: NULL output");
+    *route = t_valley_moments;
+    return TOPO_AMD_OK;
+}
+
 int topo_amd_sx_route(int* route) {
     TOPO_REQUIRE(route != nullptr, "sx_route: NULL output");
     *route = t_sx_route;
@@ -1641,6 +1648,7 @@ int topo_amd_valley_ridge_dev(const float* in, int in_rows, int in_row0, int gny
     (void)valley_ridge_reach(ksize, n_angles, &up, &down);
     Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
     TOPO_TRY(check_block(b, up, down, "valley_ridge"));
+    t_valley_moments = 0;  // (the caller's)
     forget_plane(norm_out, out_rows, nx);
     forget_plane(dir_out, out_rows, nx);
     return launch_valley_ridge(b, taps, ksize, angles, n_angles, n_planes, mean, stdev, norm_out, dir_out);
@@ -1651,6 +1659,30 @@ int topo_amd_mean_std_dev(const float* in, size_t count, double* mean, double* s
     TOPO_TRY(require_ready());
     TOPO_REQUIRE(in && mean && stdev && count >= 1, "mean_std: bad arguments");
     return launch_mean_std(in, count, mean, stdev);
+}
+
+int topo_amd_mean_std_f32_dev(const float* in, size_t count, size_t chunk, float* mean, float* stdev) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(in && mean && stdev && count >= 1, "mean_std_f32: bad arguments");
+    return launch_mean_std_np(in, count, chunk, mean, stdev);
+}
+
+int topo_amd_valley_ridge_std_dev(const float* in, int ny, int nx, const float* taps, const int32_t* ksize, const float* angles,
+                                  int n_angles, int n_planes, size_t chunk, float* norm_out, float* dir_out, float moments_out[2]) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(in && ny >= 1 && nx >= 1, "valley_ridge_std: bad DEM");
+    float mean = 0.0f, stdev = 0.0f;
+    TOPO_TRY(launch_mean_std_np(in, (size_t)ny * nx, chunk, &mean, &stdev));
+    if (moments_out) {
+        moments_out[0] = mean;
+        moments_out[1] = stdev;
+    }
+    TOPO_TRY(topo_amd_valley_ridge_dev(in, ny, 0, ny, nx, taps, ksize, angles, n_angles, n_planes, (double)mean, (double)stdev, 0, ny,
+                                       norm_out, dir_out));
+    t_valley_moments = 1;
+    return TOPO_AMD_OK;
 }
 
 // ---- gap filling: nearest valid sample along x (fill.hip; reference helpers.py:137-154 and :30-31) ---------------------
@@ -2030,6 +2062,74 @@ int topo_amd_valley_ridge_raw(const topo_amd_raster* raster, int ny, int nx, con
     TOPO_TRY(download(dir_out, d_dir, bytes));
     TOPO_HIP(hipStreamSynchronize(ctx().compute));
     return TOPO_AMD_OK;
+}
+
+// The standardised, optionally smoothed and optionally packed index of a host raster in one call: upload and decode, the
+// Gaussian of topo_amd_gaussian_dev when sigma > 0, numpy's float32 moments of that field (moments_np.hip), the index, the
+// planes encoded behind it.  One chunk, like topo_amd_valley_ridge_raw.
+int topo_amd_valley_ridge_packed(const topo_amd_raster* raster, int ny, int nx, const float* taps, const int32_t* ksize,
+                                 const float* angles, int n_angles, int n_planes, double sigma, size_t chunk,
+                                 topo_amd_plane* norm_plane, topo_amd_plane* dir_plane, float moments_out[2]) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    Source src;
+    TOPO_TRY(make_source(raster, "valley_ridge", &src));
+    OutPlane outs[2];
+    TOPO_TRY(make_out(norm_plane, "valley_ridge", &outs[0]));
+    TOPO_TRY(make_out(dir_plane, "valley_ridge", &outs[1]));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1 && outs[0] && outs[1], "valley_ridge: bad arguments");
+    TOPO_REQUIRE(sigma >= 0.0, "valley_ridge: sigma %g", sigma);
+    Context& c = ctx();
+    const size_t count = (size_t)ny * nx, bytes = count * sizeof(float);
+    HostRun run;
+    void *d_in = nullptr, *d_smooth = nullptr, *d_res[2] = {nullptr, nullptr}, *d_packed[2] = {nullptr, nullptr};
+    TOPO_TRY(run.alloc(&d_in, bytes));
+    TOPO_TRY(run.alloc(&d_res[0], bytes));
+    TOPO_TRY(run.alloc(&d_res[1], bytes));
+    if (sigma > 0.0) TOPO_TRY(run.alloc(&d_smooth, bytes));
+    for (int q = 0; q < 2; ++q) {
+        if (!outs[q].enc.plain()) TOPO_TRY(run.alloc(&d_packed[q], outs[q].bytes(ny, nx)));
+        run.prefault(outs[q].host, outs[q].bytes(ny, nx));
+    }
+    t_host_chunks = 1;
+    char* d_raw = nullptr;
+    TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    TOPO_HIP(enqueue_rows(src, d_raw, (float*)d_in, 0, ny, nx, c.compute));
+    const float* field = (const float*)d_in;
+    if (sigma > 0.0) {
+        ClassScope cls(scan_source(src, ny, nx));  // the smoothing kernels topo_amd_gauss_raw takes for this raster
+        TOPO_TRY(topo_amd_gaussian_dev(field, ny, 0, ny, nx, sigma, sigma, 0, ny, (float*)d_smooth));
+        field = (const float*)d_smooth;
+    }
+    TOPO_TRY(topo_amd_valley_ridge_std_dev(field, ny, nx, taps, ksize, angles, n_angles, n_planes, chunk, (float*)d_res[0],
+                                           (float*)d_res[1], moments_out));
+    unsigned long long* d_counts = nullptr;
+    if (d_packed[0] || d_packed[1]) {
+        void* w = nullptr;
+        TOPO_TRY(workspace(kEncodeCountsSlot, 4 * sizeof(unsigned long long), &w));
+        d_counts = (unsigned long long*)w;
+        TOPO_HIP(hipMemsetAsync(d_counts, 0, 4 * sizeof(unsigned long long), c.compute));
+        for (int q = 0; q < 2; ++q)
+            if (d_packed[q]) TOPO_TRY(launch_encode(c.compute, (const float*)d_res[q], count, outs[q].enc, d_packed[q], d_counts + 2 * q));
+    }
+    run.ready();
+    for (int q = 0; q < 2; ++q) TOPO_TRY(download(outs[q].host, d_packed[q] ? d_packed[q] : d_res[q], outs[q].bytes(ny, nx)));
+    unsigned long long counts[4] = {0, 0, 0, 0};
+    if (d_counts) TOPO_HIP(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c.compute));
+    TOPO_HIP(hipStreamSynchronize(c.compute));
+    for (int q = 0; q < 2; ++q)
+        if (d_packed[q]) {
+            outs[q].report->missing = counts[2 * q];
+            outs[q].report->saturated = counts[2 * q + 1];
+        }
+    return TOPO_AMD_OK;
+}
+
+int topo_amd_valley_ridge_std_raw(const topo_amd_raster* raster, int ny, int nx, const float* taps, const int32_t* ksize,
+                                  const float* angles, int n_angles, int n_planes, double sigma, size_t chunk, float* norm_out,
+                                  float* dir_out, float moments_out[2]) {
+    topo_amd_plane n = f32_plane(norm_out), d = f32_plane(dir_out);
+    return topo_amd_valley_ridge_packed(raster, ny, nx, taps, ksize, angles, n_angles, n_planes, sigma, chunk, &n, &d, moments_out);
 }
 
 // ---- the *_f32 entry points: the *_raw ones on float32 as stored -------------------------------------------------------------
@@ -2799,6 +2899,7 @@ int shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx, 
                        const float* angles, int n_angles, int n_planes, float* norm_out, float* dir_out, double* moments_out) {
     TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1,
                  "shard_valley_ridge: NULL argument");
+    t_valley_moments = 2;  // (the shards' float64 all-reduce)
     int above = 0, below = 0;
     (void)valley_ridge_reach(ksize, n_angles, &above, &below);
     TOPO_TRY(shard_view(&block, above, below, "shard_valley_ridge"));
@@ -2964,6 +3065,7 @@ int topo_amd_shard_valley_ridge_smoothed(float* block, int rows_local, int row0,
                  "shard_valley_ridge_smoothed: rows [%d, %d) of a raster of %d rows", row0, row0 + rows_local, gny);
     int up = 0, down = 0;
     (void)valley_ridge_reach(ksize, n_angles, &up, &down);
+    t_valley_moments = 2;  // (the shards' float64 all-reduce)
     const int g = gauss_ghost_rows(sigma);
     const int above = up + g, below = down + g;  // == topo_amd_halo_rows(VALLEY_RIDGE, kmax, sigma)
     TOPO_TRY(shard_view(&block, above, below, "shard_valley_ridge_smoothed"));

@@ -266,6 +266,8 @@ int launch_valley_ridge_mfma(const Block& b, const float* taps, const VrGroup& g
                              const int** flags_out, int* flag_cols, int* done);
 int launch_mean_std(const float* in, size_t count, double* mean, double* stdev);
 int launch_moments(const float* in, size_t count, double pivot, bool pivot_is_first_sample, double* sum, double* sumsq);
+// numpy's own float32 mean() / std() of count device floats, bit for bit (moments_np.hip); chunk: numpy's buffer size in samples
+int launch_mean_std_np(const float* in, size_t count, size_t chunk, float* mean, float* stdev);
 int launch_valley_ridge(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles,
                         int n_planes, double mean, double stdev, float* norm_out, float* dir_out);
 

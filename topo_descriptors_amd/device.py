@@ -165,6 +165,14 @@ def valley_route():
     return n.value
 
 
+def valley_moments_route():
+    """What the calling thread's last valley / ridge call did about the DEM's mean and std: 0 taken from the caller, 1 formed
+    on the device in numpy's order (``mean_std_numpy``), 2 the float64 all-reduce of a sharded call."""
+    n = C.c_int32()
+    _lib.check(_lib.lib().topo_amd_valley_moments_route(C.byref(n)), "valley_moments_route")
+    return n.value
+
+
 def sx_route():
     """The kernel route the calling thread's last Sx call took (``topo_amd_sx_route``): bits 0 - 2 the scan (0 chains down the
     columns, 1 along the rows, 2 / 3 along the diagonals (dj + 1, di + 1) / (dj + 1, di - 1), 4 the kernel without an LDS tile);
@@ -328,14 +336,38 @@ class Block:
             di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
             float(height), o0, on, planes), "sx_multi_dev")
 
-    def valley_ridge(self, taps, ksize, angles, n_planes, mean, stdev, norm, direction, out_row0=None,
+    def valley_ridge(self, taps, ksize, angles, n_planes, mean=None, stdev=None, norm=None, direction=None, out_row0=None,
                      out_rows=None):
-        """taps / ksize / angles as returned by ``topo._valley_ridge_tables``; mean / stdev of the
-        WHOLE DEM (``mean_std`` for a device-resident one)."""
+        """taps / ksize / angles as returned by ``topo._valley_ridge_tables``; mean / stdev of the WHOLE DEM, as numpy's
+        float32 ``mean()`` / ``std()`` give them.  ``None`` (both): the block must be the whole raster (``ValueError``
+        otherwise - a row block cannot know them) and they are formed on the device (``mean_std_numpy``; on the host where
+        ``helpers.moments_chunk`` says so)."""
+        from .helpers import moments_chunk  # noqa: PLC0415
+
+        if norm is None or direction is None:
+            raise ValueError("Block.valley_ridge: norm and direction planes are required")
         o0, on = self._range(out_row0, out_rows)
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         ksize = np.ascontiguousarray(ksize, dtype=np.int32)
         angles = np.ascontiguousarray(angles, dtype=np.float32)
+        if mean is None or stdev is None:
+            if mean is not None or stdev is not None:
+                raise ValueError("Block.valley_ridge: give both mean and stdev, or neither")
+            if self.row0 != 0 or self.rows != self.gny:
+                raise ValueError(f"Block.valley_ridge: rows [{self.row0}, {self.row0 + self.rows}) of a raster of {self.gny} "
+                                 "rows cannot form the whole raster's mean and stdev: pass them")
+            chunk = moments_chunk()
+            if chunk is not None and (o0, on) == (0, self.gny):
+                _lib.check(_lib.lib().topo_amd_valley_ridge_std_dev(
+                    self.data.row_ptr(self.first), self.rows, self.nx, taps.ctypes.data_as(_lib._vp),
+                    ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes), chunk,
+                    norm.ptr, direction.ptr, None), "valley_ridge_std_dev")
+                return
+            if chunk is not None:
+                mean, stdev = mean_std_numpy(self.data, chunk, self.first, self.rows)
+            else:
+                field = self.data.to_host(self.first, self.rows)
+                mean, stdev = field.mean(), field.std()
         _lib.check(_lib.lib().topo_amd_valley_ridge_dev(
             *self._head(), taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p),
             angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes), float(mean), float(stdev), o0, on,
@@ -366,6 +398,20 @@ def mean_std(array):
     _lib.check(_lib.lib().topo_amd_mean_std_dev(array.ptr, array.rows * array.nx, C.byref(m), C.byref(s)),
                "mean_std_dev")
     return m.value, s.value
+
+
+def mean_std_numpy(array, chunk=None, row0=0, rows=None):
+    """``(mean, std)`` of (rows of) a float32 DeviceArray as ``np.float32``, with the bits numpy's own ``a.mean()`` / ``a.std()``
+    give for the same samples on the host: the sums are formed on the GPU in numpy's order (``topo_amd_mean_std_f32_dev``).
+    ``chunk``: numpy's buffer size in samples (``np.getbufsize()``)."""
+    if array.dtype != np.float32:
+        raise ValueError(f"mean_std_numpy: a float32 plane, not {array.dtype}")
+    rows = array.rows - row0 if rows is None else rows
+    m, s = C.c_float(), C.c_float()
+    _lib.check(_lib.lib().topo_amd_mean_std_f32_dev(array.row_ptr(row0), rows * array.nx,
+                                                    int(np.getbufsize()) if chunk is None else int(chunk), C.byref(m), C.byref(s)),
+               "mean_std_f32_dev")
+    return np.float32(m.value), np.float32(s.value)
 
 
 def pack_sectors(sectors):

@@ -9,6 +9,7 @@ variable names, ``ds[name].dims``) is accepted, because the GPU box may not have
 import datetime
 import functools
 import logging
+import os
 import time
 
 import numpy as np
@@ -271,3 +272,77 @@ def timer(func):
         logger.info("Computed in %s (HH:mm:ss)", datetime.timedelta(seconds=time.monotonic() - start))
         return result
     return timed
+
+
+# ---- numpy's own float32 mean() / std(), restated --------------------------------------------------------------------------
+# The valley / ridge index standardises the DEM with them (reference topo.py:427) and the GPU forms them in numpy's
+# summation order (csrc/moments_np.hip, ``device.mean_std_numpy``).  This is that order in plain numpy - elementwise
+# float32 operations only, vectorised over the chunks - as the statement the kernel is held to, and as the check that the
+# numpy in this process still sums that way.
+def _pairwise_rows(blocks):
+    """numpy's pairwise sum of every row of ``blocks`` (k x m, float32)."""
+    m = blocks.shape[1]
+    if m < 8:
+        res = np.zeros(blocks.shape[0], dtype=np.float32)
+        for i in range(m):
+            res = res + blocks[:, i]
+        return res
+    if m <= 128:
+        r = blocks[:, :8].copy()
+        for j in range(1, m // 8):
+            r += blocks[:, 8 * j:8 * j + 8]
+        res = ((r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])) + ((r[:, 4] + r[:, 5]) + (r[:, 6] + r[:, 7]))
+        for i in range(m - m % 8, m):
+            res = res + blocks[:, i]
+        return res
+    half = m // 2
+    half -= half % 8
+    return _pairwise_rows(blocks[:, :half]) + _pairwise_rows(blocks[:, half:])
+
+
+def numpy_order_sum(samples, chunk):
+    """``samples.sum()`` of a 1-D float32 array as numpy forms it: chunks of ``chunk`` samples summed pairwise, the chunk
+    sums (a partial last chunk included) added one after the other from 0."""
+    full = samples.size // chunk
+    parts = [np.zeros(1, dtype=np.float32)]
+    if full:
+        parts.append(_pairwise_rows(samples[:full * chunk].reshape(full, chunk)))
+    if samples.size % chunk:
+        parts.append(_pairwise_rows(samples[None, full * chunk:]))
+    return np.add.accumulate(np.concatenate(parts), dtype=np.float32)[-1]
+
+
+def numpy_order_moments(array, chunk=None):
+    """``(array.mean(), array.std())`` of a C-contiguous float32 array, bit for bit, from the model above (``chunk``:
+    ``np.getbufsize()``)."""
+    samples = np.ascontiguousarray(array, dtype=np.float32).reshape(-1)
+    chunk = int(np.getbufsize()) if chunk is None else int(chunk)
+    n = np.float32(samples.size)
+    with np.errstate(all="ignore"):
+        mean = numpy_order_sum(samples, chunk) / n
+        dev = samples - mean
+        return mean, np.sqrt(numpy_order_sum(dev * dev, chunk) / n)
+
+
+_moments_checked = {}  # chunk -> whether this process's numpy sums as the model says
+
+
+def moments_chunk():
+    """The chunk length (``np.getbufsize()``) with which the GPU forms numpy's float32 moments, or ``None`` when the host has
+    to take them as before: ``TOPO_AMD_VALLEY_HOST_MOMENTS=1`` (read at every call), a buffer size that is no power of two
+    of 128 or more, or a numpy that does not sum as the model says (checked once per process and buffer size, on a small
+    array with a partial chunk; logged)."""
+    if os.environ.get("TOPO_AMD_VALLEY_HOST_MOMENTS") == "1":
+        return None
+    chunk = int(np.getbufsize())
+    if chunk not in _moments_checked:
+        ok = chunk >= 128 and chunk & (chunk - 1) == 0
+        if ok:
+            rng = np.random.default_rng(427)
+            probe = rng.normal(1800.0, 600.0, size=2 * chunk + 77).astype(np.float32)
+            got, want = numpy_order_moments(probe, chunk), (probe.mean(), probe.std())
+            ok = got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+        _moments_checked[chunk] = ok
+        logger.info("numpy %s float32 mean / std in chunks of %d samples: %s", np.__version__, chunk,
+                    "as modelled, formed on the GPU" if ok else "not as modelled, taken on the host")
+    return chunk if _moments_checked[chunk] else None

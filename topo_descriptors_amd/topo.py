@@ -580,28 +580,46 @@ def _valley_ridge_tables(kernels, angles):
             np.ascontiguousarray(angles, dtype=np.float32))
 
 
-def valley_ridge(dem, size, mode, flat_list=[0, 0.15, 0.3], sigma=None):  # noqa: B006 (the reference's default)
+def valley_ridge(dem, size, mode, flat_list=[0, 0.15, 0.3], sigma=None, pack=None):  # noqa: B006 (the reference's default)
     """Valley or ridge index: for 180 directions, the response of the standardised DEM to V- and
     U-shaped kernels of side ``size`` turned to that direction; returns ``[norm, direction]``, the
     largest response clipped at 0 and the direction (degrees, 0 = W-E, 90 = S-N) it came from
     (reference topo.py:389-447).  The 180 x ``len(flat_list)`` convolutions run in one pass over
-    the DEM on the GPU."""
+    the DEM on the GPU.
+
+    The reference standardises with numpy's own float32 mean / std of the whole (smoothed) array (topo.py:427).  Where that
+    array is float32 - a C-contiguous float32 ndarray, a ``PackedDem``, anything with ``sigma`` - the whole call is one library
+    call: the DEM goes up once, is smoothed there, and the two moments are formed on the GPU in numpy's summation order, bit
+    for bit (``topo_amd_valley_ridge_packed``).  An ndarray of another dtype without ``sigma`` is reduced by numpy in float64:
+    its moments stay numpy's, on the host (as do all under ``helpers.moments_chunk``'s conditions).
+
+    ``pack``: one :class:`Packing` for both planes, a pair, or a dict with the keys ``norm`` and ``direction`` (``None`` or a
+    missing key: float32); packed planes come back as :class:`PackedPlane`.  The direction plane holds whole degrees
+    0 ... 179: ``Packing(np.uint8, fill_value=255)`` stores it exactly."""
     if mode not in ("valley", "ridge"):
         raise ValueError(f"Unknown mode {mode!r}")
     values, _ = _unwrap(dem)
     _check_2d(values, "valley_ridge")
-    field = globals()["dem"](values, sigma) if sigma else values
-    keep, src, shape = _source(field)
-    # the reference standardises with numpy's own float32 mean / std of the whole array (topo.py:427); a PackedDem is the
-    # float32 array it decodes to
-    host = field.decode() if isinstance(field, _lib.PackedDem) else field
-    mean, stdev = float(host.mean()), float(host.std())
+    packs = _lib.pack_list(pack, ["norm", "direction"])
     kernels = _ridge_kernels(size, flat_list) if mode == "ridge" else _valley_kernels(size, flat_list)
     taps, ksize, angles = _valley_ridge_tables(kernels, np.arange(0, 180, dtype=np.float32))
+    tables = (taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size,
+              kernels.shape[0])
+    float32_field = bool(sigma) or isinstance(values, _lib.PackedDem) or (values.dtype == np.float32 and values.flags.c_contiguous)
+    chunk = hlp.moments_chunk() if float32_field else None
+    if chunk is not None:
+        keep, src, shape = _source(values)
+        made = [_lib.result_plane(q, shape) for q in packs]
+        _lib.check(_lib.lib().topo_amd_valley_ridge_packed(src, shape[0], shape[1], *tables, _sigma_arg(sigma), chunk,
+                                                           *[C.byref(m[1]) for m in made], None), "topo_amd_valley_ridge_packed")
+        return [_lib.wrap_plane(*m, q) for m, q in zip(made, packs)]
+    field = globals()["dem"](values, sigma) if sigma else values
+    keep, src, shape = _source(field)
+    # numpy's own mean / std on the host; a PackedDem is the float32 array it decodes to
+    host = field.decode() if isinstance(field, _lib.PackedDem) else field
+    mean, stdev = float(host.mean()), float(host.std())
     norm = _plane(shape)
     direction = _plane(shape)
-    _lib.check(_lib.lib().topo_amd_valley_ridge_raw(
-        src, shape[0], shape[1], taps.ctypes.data_as(_lib._vp),
-        ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size, kernels.shape[0], mean, stdev,
-        norm.ctypes.data_as(_lib._vp), direction.ctypes.data_as(_lib._vp)), "topo_amd_valley_ridge_raw")
-    return [norm, direction]
+    _lib.check(_lib.lib().topo_amd_valley_ridge_raw(src, shape[0], shape[1], *tables, mean, stdev, norm.ctypes.data_as(_lib._vp),
+                                                    direction.ctypes.data_as(_lib._vp)), "topo_amd_valley_ridge_raw")
+    return [p if q is None else _lib.encode_host(p, q) for p, q in zip((norm, direction), packs)]
