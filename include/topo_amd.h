@@ -537,6 +537,20 @@ int topo_amd_encode_host(const float* in, size_t count, topo_amd_plane* plane);
  * 16-byte phase with in_dev, sample by sample otherwise).  Enqueued on the compute stream; the call returns when the
  * counters are valid (it waits for the stream).                                                                          */
 int topo_amd_encode_dev(const float* in_dev, size_t count, topo_amd_plane* plane);
+/* The finishing step of a wrapper call on the device (csrc/finish.hip): the window [row0, row0 + rows) x [col0, col0 + cols)
+ * of the float32 device plane in_dev (ny x nx), with NaN put back where the uint8 device plane mask_dev (ny x nx; or NULL)
+ * is not 0, stored compactly.  plane->data is a DEVICE address of rows x cols C-contiguous samples of plane->dtype, aligned
+ * to the sample type.  For window sample (r, c) and the source index i = (row0 + r) * nx + col0 + c: the sample is NaN if
+ * mask_dev is given and mask_dev[i] != 0 (float32 bits 0x7FC00000), in_dev[i] otherwise, and is then encoded exactly as
+ * topo_amd_encode_dev encodes it.  TOPO_AMD_F32 is a real case here - the masked window copy, every unmasked sample bit
+ * for bit, a NaN's payload included; for the other types no float32 copy of the window is made.  `missing` counts the
+ * window samples stored as nodata / NaN (for TOPO_AMD_F32 too; masked samples and samples that were NaN already),
+ * `saturated` is topo_amd_encode_dev's.  Enqueued on the compute stream; the call returns when the counters are valid.
+ * rows == 0 or cols == 0: TOPO_AMD_OK, nothing is launched, both counters 0.  A window that is not inside the plane, a
+ * negative extent or a misaligned plane->data: TOPO_AMD_EINVAL.  Nothing outside the ny x nx samples of in_dev and
+ * mask_dev is read and nothing outside the rows x cols samples of plane->data is written.                               */
+int topo_amd_finish_dev(const float* in_dev, int ny, int nx, const uint8_t* mask_dev, int row0, int rows, int col0, int cols,
+                        topo_amd_plane* plane);
 /* The host-buffer entry points with packed result planes: as their *_raw namesakes with a topo_amd_plane in place of every
  * float* (NULL, or a plane whose data is NULL, where the namesake allows NULL) and an array of n planes in place of every
  * float* const*.  Every plane is, bit for bit, topo_amd_encode_host of the float32 plane the *_raw call gives; the counters

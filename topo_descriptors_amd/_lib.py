@@ -140,6 +140,7 @@ SIGNATURES = {
                                         C.c_double, C.POINTER(_vp)]),
     "topo_amd_encode_host": (C.c_int, [_vp, C.c_size_t, _pp]),
     "topo_amd_encode_dev": (C.c_int, [_vp, C.c_size_t, _pp]),
+    "topo_amd_finish_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _pp]),
     "topo_amd_tpi_std_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_double, _pp, _pp]),
     "topo_amd_tpi_std_multi_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _pp, _pp]),
     "topo_amd_gauss_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, _pp]),

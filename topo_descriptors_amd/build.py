@@ -15,7 +15,7 @@ UNITS = [("sx.hip", [], "sx.o"), ("gauss.hip", [], "gauss.o")] + \
         [(s, [], s.replace(".hip", ".o")) for s in ("disc_pair.hip", "disc.hip", "disc_wave.hip", "disc_big.hip", "valley.hip",
                                                     "moments_np.hip",
                                                     "valley_mfma.hip", "valley_fft.hip", "fill.hip", "decode.hip", "encode.hip",
-                                                    "capi.hip")]
+                                                    "finish.hip", "capi.hip")]
 SOURCES = sorted({u[0] for u in UNITS})
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

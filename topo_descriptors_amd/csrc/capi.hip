@@ -2255,6 +2255,33 @@ int topo_amd_encode_dev(const float* in_dev, size_t count, topo_amd_plane* plane
     return TOPO_AMD_OK;
 }
 
+int topo_amd_finish_dev(const float* in_dev, int ny, int nx, const uint8_t* mask_dev, int row0, int rows, int col0, int cols,
+                        topo_amd_plane* plane) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    EncodeParams p;
+    TOPO_TRY(make_encode(plane, "finish_dev", &p));
+    TOPO_REQUIRE(ny >= 0 && nx >= 0 && row0 >= 0 && rows >= 0 && col0 >= 0 && cols >= 0 && (long long)row0 + rows <= ny &&
+                     (long long)col0 + cols <= nx,
+                 "finish_dev: window rows [%d, %d + %d) x columns [%d, %d + %d) of a %d x %d plane", row0, row0, rows, col0, col0, cols, ny, nx);
+    TOPO_REQUIRE((uintptr_t)plane->data % plane_sample_bytes(p.dtype) == 0, "finish_dev: plane->data is not aligned to its sample type");
+    plane->missing = plane->saturated = 0;
+    if (rows == 0 || cols == 0) return TOPO_AMD_OK;
+    TOPO_REQUIRE(in_dev != nullptr && plane->data != nullptr, "finish_dev: NULL array");
+    Context& c = ctx();
+    dem_memo_forget(plane->data, (size_t)rows * cols * plane_sample_bytes(p.dtype));
+    void* w = nullptr;
+    TOPO_TRY(workspace(kEncodeCountsSlot, 2 * sizeof(unsigned long long), &w));
+    TOPO_HIP(hipMemsetAsync(w, 0, 2 * sizeof(unsigned long long), c.compute));
+    TOPO_TRY(launch_finish(c.compute, in_dev, nx, mask_dev, row0, rows, col0, cols, p, plane->data, (unsigned long long*)w));
+    unsigned long long counts[2] = {0, 0};
+    TOPO_HIP(hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, c.compute));
+    TOPO_HIP(hipStreamSynchronize(c.compute));
+    plane->missing = counts[0];
+    plane->saturated = counts[1];
+    return TOPO_AMD_OK;
+}
+
 int topo_amd_upload_raw(const topo_amd_raster* raster, int ny, int nx, float* out_dev) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());

@@ -128,4 +128,12 @@ int launch_encode(hipStream_t stream, const float* in, size_t count, const Encod
 // the same on host arrays (one thread: the CPU statement of the formula, not a fast path); the counters are SET
 int encode_host_array(const float* in, size_t count, const EncodeParams& p, void* out, uint64_t* missing, uint64_t* saturated);
 
+// finish.hip
+// Window [row0, row0 + rows) x [col0, col0 + cols) of the float32 plane `in` (device, nx samples a row; the caller has
+// checked that the window lies inside it) -> out (device, rows * cols compact samples of p.dtype, float32 included, aligned
+// to the sample type) on `stream`: NaN where `mask` (device, uint8, indexed like `in`; or NULL) is not 0, then encode_dev.
+// The counters as launch_encode's; for float32 counts[0] receives the NaNs stored.
+int launch_finish(hipStream_t stream, const float* in, int nx, const uint8_t* mask, int row0, int rows, int col0, int cols,
+                  const EncodeParams& p, void* out, unsigned long long* counts);
+
 }  // namespace topo

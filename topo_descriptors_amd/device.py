@@ -60,6 +60,46 @@ class DeviceArray:
         finally:
             dev.free()
 
+    def finish(self, packing=None, mask=None, window=None):
+        """The last step of a wrapper call, on the GPU (``topo_amd_finish_dev``): the ``window`` ``(row0, rows, col0, cols)`` of
+        this float32 plane (``None``: all of it) with NaN where ``mask`` - a uint8 ``DeviceArray`` of this plane's shape, or
+        ``None`` - is not 0, as a float32 ndarray or, with a ``packing``, as a ``PackedPlane`` whose counters are those of the
+        window.  Only the window crosses the link.  With neither a mask nor a window it is :meth:`to_host` /
+        :meth:`to_packed`; an empty window gives a zero-size result without a GPU call."""
+        if self.dtype != np.float32:
+            raise ValueError(f"DeviceArray.finish: a float32 plane is finished, not {self.dtype}")
+        if packing is not None and not isinstance(packing, _lib.Packing):
+            raise ValueError(f"DeviceArray.finish: {packing!r} is not a Packing")
+        if mask is not None:
+            if not isinstance(mask, DeviceArray) or mask.dtype != np.uint8:
+                raise ValueError("DeviceArray.finish: the mask is a uint8 DeviceArray")
+            if (mask.rows, mask.nx) != (self.rows, self.nx):
+                raise ValueError(f"DeviceArray.finish: a {mask.rows} x {mask.nx} mask for a {self.rows} x {self.nx} plane")
+        if window is None:
+            if mask is None:
+                return self.to_host() if packing is None else self.to_packed(packing)
+            window = (0, self.rows, 0, self.nx)
+        try:
+            row0, rows, col0, cols = (int(v) for v in window)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"DeviceArray.finish: window {window!r} is not (row0, rows, col0, cols)") from exc
+        if min(row0, rows, col0, cols) < 0 or row0 + rows > self.rows or col0 + cols > self.nx:
+            raise ValueError(f"DeviceArray.finish: window rows [{row0}, {row0} + {rows}) x columns [{col0}, {col0} + {cols}) of a "
+                             f"{self.rows} x {self.nx} plane")
+        stored = _lib.Packing(np.float32) if packing is None else packing
+        if rows == 0 or cols == 0:
+            values = np.empty((rows, cols), dtype=stored.dtype)
+            return values if packing is None else _lib.PackedPlane(values, packing, 0, 0)
+        dev = DeviceArray(rows, cols, dtype=stored.dtype)
+        try:
+            plane = stored.struct(dev.ptr)
+            _lib.check(_lib.lib().topo_amd_finish_dev(self.ptr, self.rows, self.nx, None if mask is None else mask.ptr,
+                                                      row0, rows, col0, cols, C.byref(plane)), "finish_dev")
+            values = dev.to_host()
+            return values if packing is None else _lib.PackedPlane(values, packing, plane.missing, plane.saturated)
+        finally:
+            dev.free()
+
     def upload_rows(self, array, row0=0):
         a = np.ascontiguousarray(array, dtype=self.dtype)
         _lib.check(_lib.lib().topo_amd_memcpy_h2d(self.row_ptr(row0), _lib.ptr(a), a.nbytes),
@@ -336,6 +376,17 @@ class Block:
             di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
             float(height), o0, on, planes), "sx_multi_dev")
 
+    def moments(self):
+        """numpy's float32 ``(mean(), std())`` of this block's rows, as the valley / ridge index standardises with them: formed
+        on the device in numpy's order (``mean_std_numpy``), or on the host where ``helpers.moments_chunk`` says so."""
+        from .helpers import moments_chunk  # noqa: PLC0415
+
+        chunk = moments_chunk()
+        if chunk is not None:
+            return mean_std_numpy(self.data, chunk, self.first, self.rows)
+        field = self.data.to_host(self.first, self.rows)
+        return field.mean(), field.std()
+
     def valley_ridge(self, taps, ksize, angles, n_planes, mean=None, stdev=None, norm=None, direction=None, out_row0=None,
                      out_rows=None):
         """taps / ksize / angles as returned by ``topo._valley_ridge_tables``; mean / stdev of the WHOLE DEM, as numpy's
@@ -363,11 +414,7 @@ class Block:
                     ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes), chunk,
                     norm.ptr, direction.ptr, None), "valley_ridge_std_dev")
                 return
-            if chunk is not None:
-                mean, stdev = mean_std_numpy(self.data, chunk, self.first, self.rows)
-            else:
-                field = self.data.to_host(self.first, self.rows)
-                mean, stdev = field.mean(), field.std()
+            mean, stdev = self.moments()
         _lib.check(_lib.lib().topo_amd_valley_ridge_dev(
             *self._head(), taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p),
             angles.ctypes.data_as(_lib._vp), ksize.size, int(n_planes), float(mean), float(stdev), o0, on,

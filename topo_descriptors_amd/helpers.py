@@ -55,6 +55,13 @@ def get_da(dem_ds):
     return dem_ds[list(dem_ds)[0]]
 
 
+def dem_shape(dem_ds):
+    """``(ny, nx)`` of the Dataset's first data variable (an ndarray, or a ``PackedDem``)."""
+    values = get_da(dem_ds).values
+    ny, nx = values.shape if hasattr(values, "shape") else np.shape(values)
+    return int(ny), int(nx)
+
+
 def round_up_to_odd(f):
     """Nearest odd integer as int64 (reference helpers.py:108-111)."""
     f = np.asarray(f, dtype=np.float64)
@@ -170,6 +177,54 @@ def get_sigmas(smth_factors, scales_pxl):
     factors = np.array([f if f else np.nan for f in smth_factors], dtype=np.float64)
     sigmas = factors * np.asarray(scales_pxl) / CFG.scale_std
     return [None if np.isnan(s) else s for s in sigmas]
+
+
+# ---- the crop of the reference's writer (helpers.py:34-65: ``.sel(crop)``), restated on plain coordinates ------------------------
+def _axis_window(coords, bounds, key):
+    """``(first, count)`` of the labels ``Dataset.sel({key: bounds})`` keeps: ``pandas.Index.slice_indexer`` on a strictly
+    monotonic index - label-based, both ends inclusive, a bound need not be a label."""
+    n = coords.size
+    if bounds is None:
+        return 0, n
+    if not isinstance(bounds, slice):
+        raise NotImplementedError(f"crop[{key!r}] = {bounds!r}: only slice(start, stop) selections are supported")
+    if bounds.step is not None:
+        raise NotImplementedError(f"crop[{key!r}] = {bounds!r}: a slice with a step is not supported")
+    if n and coords[0] > coords[-1]:  # decreasing: labels <= start and >= stop
+        asc = coords[::-1]
+        first = 0 if bounds.start is None else n - int(np.searchsorted(asc, bounds.start, side="right"))
+        last = n if bounds.stop is None else n - int(np.searchsorted(asc, bounds.stop, side="left"))
+    else:  # increasing: labels >= start and <= stop
+        first = 0 if bounds.start is None else int(np.searchsorted(coords, bounds.start, side="left"))
+        last = n if bounds.stop is None else int(np.searchsorted(coords, bounds.stop, side="right"))
+    return first, max(last - first, 0)
+
+
+def crop_window(dem_ds, crop):
+    """``(row0, rows, col0, cols)``: the part of the DEM that ``dem_ds.sel(crop)`` selects (the reference's writer,
+    helpers.py:34-65), from the 1-D ``y`` and ``x`` coordinates alone - no xarray needed.  ``crop``: ``None`` or a dict with
+    the keys ``"x"`` / ``"y"`` (a missing key: the whole axis) and ``slice(start, stop)`` values, label-based with both ends
+    inclusive and ``None`` for an open end, as ``pandas.Index.slice_indexer`` selects: on an increasing coordinate the labels
+    ``>= start`` and ``<= stop``, on a decreasing one the labels ``<= start`` and ``>= stop``.  A slice in the wrong direction
+    for its coordinate (``slice(-160000, 480000)`` on a north-to-south ``y``) selects nothing, as in the reference: ``rows`` or
+    ``cols`` is 0.  ``KeyError`` for another key, ``NotImplementedError`` for a value that is no slice or has a step,
+    ``ValueError`` for a coordinate that is not strictly monotonic or does not have the array's length."""
+    check_dem(dem_ds)
+    ny, nx = dem_shape(dem_ds)
+    crop = {} if crop is None else dict(crop)
+    for key in crop:
+        if key not in ("x", "y"):
+            raise KeyError(f"crop: {key!r} is not a dimension of the DEM ('x' or 'y')")
+    window = []
+    for key, n in (("y", ny), ("x", nx)):
+        coords = np.asarray(dem_ds[key].values)
+        if coords.ndim != 1 or coords.size != n:
+            raise ValueError(f"crop: {key} has {coords.shape} coordinates for {n} samples")
+        step = np.diff(coords)
+        if not ((step > 0).all() or (step < 0).all()):
+            raise ValueError(f"crop: the {key} coordinate must be strictly monotonic (increasing or decreasing)")
+        window.append(_axis_window(coords, crop.get(key), key))
+    return window[0] + window[1]
 
 
 # ---- the steps either side of the path (SURVEY 8f n4): thin, and xarray's where the reference uses it
