@@ -4,7 +4,7 @@ With TOPO_AMD_HALO_LOOPBACK=1 and a communicator of one rank, ``topo_amd_halo_ex
 its real ``ncclSend`` / ``ncclRecv`` pairs to rank 0 itself, with periodic wrap: the block's last
 ``halo_above`` rows land in its top ghost rows, its first ``halo_below`` rows in its bottom ghost rows.
 Pointer offsets, element counts, the ``input_ready`` / ``halo_done`` stream ordering and the 16-CU
-reservation of ``run_overlapped`` therefore run on hardware.  A middle shard whose two neighbours are
+reservation of ``run_three`` therefore run on hardware.  A middle shard whose two neighbours are
 itself is the middle third of the DEM stacked three times, which gives the sharded entry points an
 exact single-block answer to be compared with, bit for bit.  (Precedent for independent blocks plus
 ghost rows in the reference: ``map_overlap(..., boundary="none")``, topo.py:177-178.)"""
@@ -47,7 +47,7 @@ def test_ghosts_are_the_wrapped_rows_three_steps(loopback_comm):
         _lib.check(lib.topo_amd_memset(buf.ptr, 0xFF, buf.nbytes), "memset")
         buf.upload_rows(local, above)
         _lib.check(lib.topo_amd_halo_exchange_start(buf.ptr, rows, nx, above, below), "halo_exchange_start")
-        # an interior launch on the owned rows while the exchange is in flight (what run_overlapped does)
+        # an interior launch on the owned rows while the exchange is in flight (what run_three does)
         blk = d.Block(buf, row0=0, gny=rows, first_buffer_row=above, rows=rows)
         blk.tpi_std(67, tpi=tpi)
         _lib.check(lib.topo_amd_halo_wait(), "halo_wait")
@@ -122,7 +122,7 @@ def _poison_ghosts(sd):
 # sigma 0.75: Sobel, 1 ghost row.  2.25 / 3.25: matrix-core route below radius 16, 17 ghost rows (ADVICE r02, high:
 # the shard used to be laid out with R + 1).  1.5: vector-ALU route (radius 6).  7.0: matrix cores, radius 28.
 # (3.25, 2.0): anisotropic, two smooths.  30.25 on 8800 local rows: row chunks + the epilogue on the second stream
-# inside run_overlapped.
+# inside run_three.
 @pytest.mark.parametrize("sigma,ratio,rows,nx", [(0.75, 1.0, 256, 512), (1.5, 1.0, 256, 512), (2.25, 1.0, 300, 512),
                                                  (3.25, 1.0, 300, 512), (3.25, 1.0, 263, 516), (7.0, 1.0, 300, 512),
                                                  (3.25, 2.0, 300, 512), (30.25, 1.0, 8800, 512)])

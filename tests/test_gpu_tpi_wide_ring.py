@@ -19,7 +19,7 @@ WIDE_SIZES = [67]  # the route's sizes (csrc/disc_wave_impl.hpp: tpi_wide_min_si
 
 
 def lattice_samples(dem):
-    """The samples the raster class is taken from (csrc/capi.hip, scan_block: rows step_r / 2 + i step_r, columns
+    """The samples the raster class is taken from (csrc/raster_class.hip, scan_block: rows step_r / 2 + i step_r, columns
     step_c / 2 + j step_c, step = max(1, extent / 128))."""
     gny, nx = dem.shape
     sr, sc = max(1, gny // 128), max(1, nx // 128)

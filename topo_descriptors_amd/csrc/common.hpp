@@ -77,7 +77,7 @@ struct Seams {
 // The other form of a sharded call, for kernels whose tiles are independent (Sx, the Gaussian passes): ONE launch over
 // all the rows the shard owns, on the block with its ghost rows.  The launcher puts the tile rows that read ghost
 // rows (global rows < ghost_lo or >= ghost_hi) at the end of the dispatch order, and their blocks wait at the gate.
-// A launcher that cannot do that answers TOPO_AMD_EUNSUP BEFORE it launches anything (capi.hip then runs the
+// A launcher that cannot do that answers TOPO_AMD_EUNSUP BEFORE it launches anything (shard.hip then runs the
 // interior and the seam strips as separate launches); one that can clears `armed`.
 struct GhostGate {
     bool armed = false;
@@ -96,12 +96,12 @@ struct Context {
     int device = -1;
     int num_cu = 256;
     int reserve_cus = 0;  // CUs persistent kernels leave free while a ghost-row exchange is in flight
-    Seams seams;          // set by run_fused (capi.hip) around the launchers of one sharded call
-    GhostGate ghost;      // set by run_gated (capi.hip) around the launcher of one sharded call
+    Seams seams;          // set by run_fused (shard.hip) around the launchers of one sharded call
+    GhostGate ghost;      // set by run_gated (shard.hip) around the launcher of one sharded call
     uint32_t* gate_word = nullptr;      // device word the communication stream writes the exchange epoch into
     uint32_t* gate_timeouts = nullptr;  // pinned host word (see Gate)
     uint32_t gate_epoch = 0;            // epoch of the last exchange started
-    // How the seam parts wait (capi.hip, run_fused).  The library starts CAREFUL: a block waits a short while at a
+    // How the seam parts wait (shard.hip, run_fused).  The library starts CAREFUL: a block waits a short while at a
     // closed gate, then leaves its seam tiles to a clean-up launch behind the exchange's event - correct whatever
     // RCCL's kernel needs to make progress.  After a few careful calls in which no block gave up (the exchange does
     // run next to the interior launch on this machine) it goes LEAN: no clean-up launch and no event wait on the
@@ -119,7 +119,7 @@ struct Context {
     // mapped memory ran at half the link's rate: profiles/r05_host_pipeline.txt).  topo_amd_release_host_planes frees them.
     std::vector<void*> host_planes;
     std::vector<size_t> host_plane_bytes;
-    hipStream_t up = nullptr, down = nullptr;  // the copies of a pipelined host-buffer call (capi.hip, run_pipelined; created on first use)
+    hipStream_t up = nullptr, down = nullptr;  // the copies of a pipelined host-buffer call (host_api.hip, run_pipelined; created on first use)
     std::vector<hipEvent_t> pipe_events;        // its events: uploaded chunk k, computed chunk k
     hipStream_t aux = nullptr;       // bandwidth-bound epilogues running next to matrix-core kernels (created on first use)
     hipEvent_t aux_ready[64] = {};    // compute -> aux, one per chunk
@@ -289,7 +289,7 @@ struct RasterClass {
     float lo = 0.0f, hi = 4096.0f;  // smallest / largest ordinary lattice sample (finite, within +-2^18); lo > hi: none seen
     float frac_share = 0.0f;        // share of the lattice samples with a fractional part (TIME only: which disc kernels go first)
 };
-RasterClass current_class();  // of the call in flight on this thread (capi.hip sets it around the launchers)
+RasterClass current_class();  // of the call in flight on this thread (ClassScope, capi.hpp, sets it around the launchers)
 
 // What the library remembers about the blocks it has seen (keyed by block pointer, rows and width; a few entries) - TIME
 // only, never bits: the share of tiles with fractional elevations in one block's run of the last TPI call, written by

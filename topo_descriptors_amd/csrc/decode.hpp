@@ -1,6 +1,6 @@
 // The decode of a stored raster sample (include/topo_amd.h, "raw sources"), stated once for the host and once for the
 // device.  Everything that turns a stored sample into the float32 the kernels read - the decode kernel (decode.hip),
-// topo_amd_decode_host and the raster-class scan of a caller's array (capi.hip) - goes through these two templates.
+// topo_amd_decode_host and the raster-class scan of a caller's array (raster_class.hip) - goes through these two templates.
 //
 //     value = NaN                                       if has_nodata and (double)raw == nodata
 //     value = (float) ( (double)raw * scale + offset )  otherwise

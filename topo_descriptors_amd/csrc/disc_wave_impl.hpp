@@ -67,7 +67,7 @@ struct WaveArgs {
     int32_t* tile_c;    // ... and the offset c of every tile that has them
 };
 
-// One launch, several row blocks ("parts").  An ordinary call has one part.  A sharded call (capi.hip, run_fused)
+// One launch, several row blocks ("parts").  An ordinary call has one part.  A sharded call (shard.hip, run_fused)
 // has the rows whose stencils stay inside the shard as part 0 and the seam strips - the rows that read ghost rows -
 // as parts 1 and 2, each with the block view, the output rows and the slices of the workspaces that the separate
 // launches of rounds 1-3 gave it (so the bits cannot differ).  Every persistent block walks its share of part 0,

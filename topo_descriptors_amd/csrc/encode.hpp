@@ -1,6 +1,6 @@
 // The encode of a float32 result sample into the type a file stores it in (include/topo_amd.h, "packed result planes"),
 // stated once for the host and once for the device.  Everything that packs a result plane - the encode kernel (encode.hip),
-// topo_amd_encode_host, topo_amd_encode_dev and the row chunks of the *_packed entry points (capi.hip) - goes through these
+// topo_amd_encode_host, topo_amd_encode_dev and the row chunks of the *_packed entry points (host_api.hip) - goes through these
 // two templates.  For an integer type T, [lo, hi] being T's range without the nodata code:
 //
 //     code = nodata                                  if v is NaN                      (counted in `missing`)
