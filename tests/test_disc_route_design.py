@@ -6,7 +6,65 @@ import numpy as np
 import pytest
 
 from oracle import topo_oracle as orc
+import test_gpu_disc_routes as routes
 from test_gpu_disc_routes import Reference, check_nans, check_std, check_tpi, raster, reference, shape_of
+
+
+# ---- the route word of every odd size, from the thresholds ``ROUTES`` documents ---------------------------------------------
+TPI_RING_MAX = 17        # TPI alone: the ring build, 5 ... 17 px (below 17 px without it: one marching kernel, no second pass)
+STD_SPEC_WIDE_MAX = 13   # TPI + STD on whole metres: the 512-column build (STD alone from 2^27 pixels and up to 7 px only)
+STD_SPEC_BOTH_MAX = 21   # the second pass over fractional tiles in the form with staging waves apart
+STD_RING_BOTH_MAX = 41   # ... in the ring kernel's form; up to here the first pass has staging waves apart (tiles of 48 rows)
+STD_RING_MAX = 67        # STD / TPI + STD: the ring kernel
+FULL_TILE_MAX = 77       # LDS holds the 60-row tile of the marching kernels
+
+
+def tile_rows(size, nwaves, cap):
+    """Rows of a tile of the marching (12 waves, at most 60) and general (8 waves, at most 64) kernels: what 160 KiB hold."""
+    th = cap
+    while th > nwaves and (th + size + nwaves) * 256 * 4 + (th * (size + 1) + 8) * 2 + 16 > 160 * 1024:
+        th -= nwaves
+    return th
+
+
+def route_rule(size, op, cls, one_block=True, big=False):
+    """The kernels (``ROUTES``' part of the word) of an odd ``size`` from 3 to 101, ``op`` of ``OPS`` and raster class ``cls``
+    (0 whole metres, 1 at most half fractional, 2 mostly fractional); ``big``: a call of 2^27 pixels or more."""
+    assert size % 2 == 1 and 3 <= size <= 101
+    r = routes
+    th12, th8 = tile_rows(size, 12, 60), tile_rows(size, 8, 64)
+    assert (th12 == 60) == (size <= FULL_TILE_MAX)
+    if op == "tpi":
+        if 5 <= size <= TPI_RING_MAX:
+            return r.kernels(r.F_RING, 64, r.FR_RING_BOTH | r.DEFERRED)
+        if size < TPI_RING_MAX:
+            return r.kernels(r.F_MARCH, th12, r.DEFERRED)
+        if size == 67 and cls == 0 and one_block:
+            return r.kernels(r.F_WIDE, 64, r.SCALED | r.DEFERRED) | r.WIDE_BIT
+        if cls == 2:
+            return r.kernels(r.F_SCALED_ALL, th12, r.DEFERRED)
+        return r.kernels(r.F_MARCH, th12, r.SCALED | r.DEFERRED)
+    if 5 <= size <= STD_RING_MAX:
+        if cls == 2 and size > STD_RING_BOTH_MAX:
+            return r.kernels(r.F_SUMS, th12, r.STD_MARCH | r.FR_MARCH | r.DEFERRED)
+        spec = size <= STD_RING_BOTH_MAX
+        if cls == 0 and size <= STD_SPEC_WIDE_MAX and (op == "tpi_std" or (size <= 7 and big)):
+            return r.kernels(r.F_SPEC8, 48, r.DEFERRED)
+        second = r.FR_SPEC_BOTH if size <= STD_SPEC_BOTH_MAX else r.FR_STD_RING_BOTH if size <= STD_RING_BOTH_MAX else 0
+        return r.kernels(r.F_SPEC4 if spec else r.F_STD_RING, 48 if spec else 60, second | r.DEFERRED)
+    if size >= 31 and th12 == 60:
+        return r.kernels(r.F_MARCH, th12, r.STD_MARCH | r.DEFERRED)
+    return r.kernels(r.F_GENERAL, th8, 0)
+
+
+def test_route_rule_reproduces_the_pinned_routes():
+    assert sorted(routes.ROUTES) == list(routes.SIZES)
+    for size, by_op in routes.ROUTES.items():
+        for op, by_class in zip(routes.OPS, by_op):
+            for cls, word in enumerate(by_class):
+                assert route_rule(size, op, cls) == word, (size, op, cls, hex(route_rule(size, op, cls)), hex(word))
+    assert route_rule(67, "tpi", 0, one_block=False) == routes.MARCH_SCALED
+    assert route_rule(7, "std", 0, big=True) == routes.SPEC8 and route_rule(9, "std", 0, big=True) == routes.SPEC4_SPEC
 
 
 def shifted(field, dj, di):

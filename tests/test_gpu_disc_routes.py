@@ -296,6 +296,28 @@ def test_route_values_and_footprint(size, kind):
             assert s is None or same_bits(s.astype(np.float64), got[op][1]), (op, cuts, "std")
 
 
+# ---- every odd size from 3 to 101 -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["hard_whole", "hard_frac"])
+@pytest.mark.parametrize("size", range(3, 103, 2))
+def test_every_odd_size_takes_its_route(size, kind):
+    """The sizes between the pinned ones: the word is the one ``route_rule`` (tests/test_disc_route_design.py) derives from the
+    thresholds, on the wave-shift launcher - a size its translation unit does not build would fall through to the gather
+    kernel or the prefix planes with correct values - and the requests agree in their bits.  160 x 520: several tile rows at
+    every tile height from 36 to 64, two strips at the 256-, 384- and 512-column widths.  No oracle here."""
+    from test_disc_route_design import route_rule  # (that module imports this one)
+
+    dem = raster(kind, *SMALL)
+    got = {}
+    for op in OPS:
+        t, s, route = host_call(op, dem, size)
+        want = WAVE | WANT[op] | route_rule(size, op, CLASS[kind])
+        assert route == want, (op, hex(route), hex(want))
+        got[op] = (t, s)
+    assert same_bits(got["std"][1], got["tpi_std"][1])
+    if kind == "hard_whole":
+        assert same_bits(got["tpi"][0], got["tpi_std"][0])
+
+
 # ---- widths that are no multiple of 4: the re-pitched copy ------------------------------------------------------------------
 @pytest.mark.parametrize("width", [1038, 1041])
 @pytest.mark.parametrize("kind", ["patch", "hard_frac"])

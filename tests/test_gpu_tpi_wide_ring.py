@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from topo_descriptors_amd import _lib, device as d, shard  # noqa: E402
 
-WIDE_SIZES = [67]  # the route's sizes (csrc/disc_wave_impl.hpp: tpi_wide_min_size ... tpi_wide_max_size)
+WIDE_SIZES = [67]  # the route's sizes (csrc/disc_wave_impl.hpp: tpi_takes_wide_ring)
 
 
 def lattice_samples(dem):

@@ -638,27 +638,14 @@ template <int SIZE, int NCR, int MODE, int SIZE2 = 0>
 int launch_ring(const Block& b, float* tpi_out, float* tpi2_out = nullptr) {
     using G = RGeo<SIZE, NCR>;
     using C = RingCfg<SIZE, NCR>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, nullptr, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0, 0, tpi2_out};
+    WaveArgs a = wave_args(b, tpi_out, nullptr);
+    a.tpi2 = tpi2_out;
     constexpr size_t kLds = C::LDS + (MODE == kRingBoth ? (size_t)C::R * G::W * sizeof(uint32_t) : 0);
     static_assert(kLds <= 160 * 1024, "the two rings do not fit LDS");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_ring_kernel<SIZE, NCR, MODE, SIZE2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)tpi_ring_kernel<SIZE, NCR, MODE, SIZE2>,
-                                                              C::NW * 64, kLds));
-        blocks_per_cu = nblk < 1 ? 1 : (nblk > 4 ? 4 : nblk);  // small discs: several rings per CU
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, C::TH, G::TILE_W, true, MODE == kRingMainFrac || MODE == kRingFraction, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(tpi_ring_kernel<SIZE, NCR, MODE, SIZE2>, tpi_ring_kernel_parts<SIZE, NCR, MODE, SIZE2>, grid, C::NW * 64, kLds, ps, tiles_x);
+    // (small discs: several rings per CU, four at the most)
+    return launch_tiles(tpi_ring_kernel<SIZE, NCR, MODE, SIZE2>, tpi_ring_kernel_parts<SIZE, NCR, MODE, SIZE2>, &blocks_per_cu, C::NW * 64,
+                        kLds, 4, b, a, C::TH, G::TILE_W, true, MODE == kRingMainFrac || MODE == kRingFraction);
 }
 
 
@@ -1203,7 +1190,7 @@ struct StdSpecCfg {
 // the second pass for fractional elevations (std_ring_kernel's kStdBoth: a third image, the three chains, the general
 // kernel's expressions) in this form: the three images of SIZE + 32 rows fit up to 21 px
 // the 512-column build: two images of SIZE + 32 rows of 2 KiB
-// (used for 5 and 7 px, and for TPI + STD up to 13 px: launch_wave_any)
+// (used for 5 and 7 px, and for TPI + STD up to 13 px: std_takes_spec_wide, disc_wave_impl.hpp)
 constexpr bool std_spec_wide_fits(int size) { return std_ring_spec(size) && size <= 13; }
 constexpr bool std_spec_both_fits(int size) { return std_ring_spec(size) && (size_t)(size + 32) * 768 * 4 + 512 <= 160 * 1024; }
 
@@ -1594,24 +1581,11 @@ template <int SIZE, bool WANT_TPI, bool BOTH = false, int NCR = 4>
 int launch_std_ring_spec(const Block& b, float* tpi_out, float* std_out) {
     using G = RGeo<SIZE, NCR>;
     using C = StdSpecCfg<SIZE, BOTH, NCR>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0, 0};
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)std_ring_spec_kernel<SIZE, WANT_TPI, BOTH, NCR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)std_ring_spec_kernel<SIZE, WANT_TPI, BOTH, NCR>, C::NW * 64, C::LDS));
-        blocks_per_cu = nblk < 1 ? 1 : (nblk > 2 ? 2 : nblk);
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
+    WaveArgs a = wave_args(b, tpi_out, std_out);
     a.report = BOTH ? nullptr : dem_memo_report(b);
-    TOPO_TRY(make_parts(b, a, C::TH, G::TILE_W, true, false, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(std_ring_spec_kernel<SIZE, WANT_TPI, BOTH, NCR>, std_ring_spec_kernel_parts<SIZE, WANT_TPI, BOTH, NCR>, grid, C::NW * 64, C::LDS, ps, tiles_x);
+    static int blocks_per_cu = 0;
+    return launch_tiles(std_ring_spec_kernel<SIZE, WANT_TPI, BOTH, NCR>, std_ring_spec_kernel_parts<SIZE, WANT_TPI, BOTH, NCR>, &blocks_per_cu,
+                        C::NW * 64, C::LDS, 2, b, a, C::TH, G::TILE_W, true, false);
 }
 
 template <int SIZE, bool WANT_TPI, int MODE = kStdMain>
@@ -1620,26 +1594,12 @@ int launch_std_ring(const Block& b, float* tpi_out, float* std_out) {
     using C = StdRingCfg<SIZE>;
     constexpr size_t kLds = C::LDS + (MODE == kStdBoth ? (size_t)C::R * G::W * sizeof(uint32_t) : 0);
     static_assert(kLds <= 160 * 1024, "the three images do not fit LDS");
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0, 0};
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)std_ring_kernel<SIZE, WANT_TPI, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)kLds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)std_ring_kernel<SIZE, WANT_TPI, MODE>, C::NW * 64,
-                                                              kLds));
-        blocks_per_cu = nblk < 1 ? 1 : (nblk > 2 ? 2 : nblk);  // small discs: two rings per CU
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
+    WaveArgs a = wave_args(b, tpi_out, std_out);
     a.report = MODE == kStdMain ? dem_memo_report(b) : nullptr;
-    TOPO_TRY(make_parts(b, a, C::TH, G::TILE_W, true, false, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    TOPO_TRY(launch_parts(std_ring_kernel<SIZE, WANT_TPI, MODE>, std_ring_kernel_parts<SIZE, WANT_TPI, MODE>, grid, C::NW * 64, kLds, ps, tiles_x));
+    static int blocks_per_cu = 0;
+    // (small discs: two rings per CU)
+    TOPO_TRY(launch_tiles(std_ring_kernel<SIZE, WANT_TPI, MODE>, std_ring_kernel_parts<SIZE, WANT_TPI, MODE>, &blocks_per_cu, C::NW * 64,
+                          kLds, 2, b, a, C::TH, G::TILE_W, true, false));
     return TOPO_AMD_OK;
 }
 

@@ -580,28 +580,17 @@ int launch_ring_wide(const Block& b, float* tpi_out, int map_th, int map_tw) {
     using C = WideCfg<SIZE>;
     Context& c = ctx();
     TOPO_REQUIRE(c.seams.n == 0, "the wide ring takes single-block calls only");
-    WaveArgs a{b.in, tpi_out, nullptr, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0, 0};
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_ring_wide_kernel<SIZE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)tpi_ring_wide_kernel<SIZE>, C::NW * 64, C::LDS));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
+    WaveArgs a = wave_args(b, tpi_out, nullptr);
     a.report = dem_memo_report(b);
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, C::TH, G::TILE_W, true, false, &ps, &tiles_x, &ntiles, map_th, map_tw));
-    TOPO_REQUIRE(ps.n == 1 && ps.a[0].map_th == map_th && ps.a[0].map_tw == map_tw, "wide ring: tile map of another geometry");
-    const size_t map_bytes = (size_t)((b.nx + map_tw - 1) / map_tw) * ps.a[0].map_tiles_y;
-    TOPO_HIP(hipMemsetAsync(ps.a[0].defer, kTileDone, map_bytes, c.compute));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    hipLaunchKernelGGL(tpi_ring_wide_kernel<SIZE>, dim3((unsigned)grid), dim3(C::NW * 64), C::LDS, c.compute, ps.a[0], tiles_x, ps.tiles_y[0], ps.run[0]);
-    TOPO_HIP(hipGetLastError());
-    return TOPO_AMD_OK;
+    static int blocks_per_cu = 0;
+    const auto clear_map = [&](WaveParts& ps, long) -> int {
+        TOPO_REQUIRE(ps.n == 1 && ps.a[0].map_th == map_th && ps.a[0].map_tw == map_tw, "wide ring: tile map of another geometry");
+        const size_t map_bytes = (size_t)((b.nx + map_tw - 1) / map_tw) * ps.a[0].map_tiles_y;
+        TOPO_HIP(hipMemsetAsync(ps.a[0].defer, kTileDone, map_bytes, c.compute));
+        return TOPO_AMD_OK;
+    };
+    return launch_tiles(tpi_ring_wide_kernel<SIZE>, nullptr, &blocks_per_cu, C::NW * 64, C::LDS, 0, b, a, C::TH, G::TILE_W, true, false,
+                        map_th, map_tw, clear_map);
 }
 
 }  // namespace

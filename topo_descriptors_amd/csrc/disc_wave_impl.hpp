@@ -1380,73 +1380,82 @@ int launch_parts(K1 kernel_one, K kernel, long grid, int threads, size_t lds, Wa
             return TOPO_AMD_OK;
         }
     }
-    TOPO_REQUIRE(ps.gate.word == nullptr || (size_t)grid <= kGateSlots, "a gated launch of %ld blocks (at most %zu)", grid, kGateSlots);
-    // (a kernel that serves ordinary calls too had its LDS size set by its launcher, once)
-    if constexpr (!std::is_same<K1, std::nullptr_t>::value)
-        TOPO_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, c.compute, ps, tiles_x);
-    TOPO_HIP(hipGetLastError());
-    if (ps.gate.word != nullptr && ps.gate.errors == nullptr) {  // (lean mode: no clean-up, see Context::gate_mode)
-        TOPO_TRY(topo_amd_halo_wait());
-        ps.gate.word = nullptr;
-        ps.cleanup = 1;
+    if constexpr (std::is_same<K, std::nullptr_t>::value) {  // (the wide ring: its launcher has refused a sharded call)
+        TOPO_REQUIRE(false, "a kernel for ordinary calls only on a call of %d parts", ps.n);
+    } else {
+        TOPO_REQUIRE(ps.gate.word == nullptr || (size_t)grid <= kGateSlots, "a gated launch of %ld blocks (at most %zu)", grid, kGateSlots);
+        // (a kernel that serves ordinary calls too had its LDS size set by its launcher, once)
+        if constexpr (!std::is_same<K1, std::nullptr_t>::value)
+            TOPO_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, c.compute, ps, tiles_x);
         TOPO_HIP(hipGetLastError());
+        if (ps.gate.word != nullptr && ps.gate.errors == nullptr) {  // (lean mode: no clean-up, see Context::gate_mode)
+            TOPO_TRY(topo_amd_halo_wait());
+            ps.gate.word = nullptr;
+            ps.cleanup = 1;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, c.compute, ps, tiles_x);
+            TOPO_HIP(hipGetLastError());
+        }
     }
     return TOPO_AMD_OK;
 }
 
-template <int SIZE, int TH, int NWAVES, bool OUT_TPI, bool OUT_SUM, bool ALLOW_FRAC = false>
-int launch_march(const Block& b, float* tpi_out, bool scaled = false) {
-    using G = Geo<SIZE>;
+// What the launchers of the marching, ring and general kernels share.  `kernel_one` is the form for an ordinary call
+// (nullptr: `kernel`, the parts form, serves every call).  `blocks_per_cu` is the launcher's own static word, one per kernel
+// instantiation: 0 until the first use, which sets the kernel's LDS size and asks the occupancy (`cap`: at most so many
+// blocks per CU, 0 = as many as fit).  tile_h ... map_tw: make_parts.  `prepare(ps, grid)` is what a launcher has to do
+// between sizing the grid and the launch.
+struct NoPrepare {
+    int operator()(WaveParts&, long) const { return TOPO_AMD_OK; }
+};
+inline WaveArgs wave_args(const Block& b, float* tpi_out, float* std_out) {  // (every other field zero)
+    return WaveArgs{b.in, tpi_out, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows};
+}
+template <class K1, class K, class Prepare = NoPrepare>
+int launch_tiles(K1 kernel_one, K kernel, int* blocks_per_cu, int threads, size_t lds, int cap, const Block& b, const WaveArgs& a,
+                 int tile_h, int strip_w, bool want_defer, bool want_sums, int map_th = 0, int map_tw = 0, Prepare prepare = {}) {
     Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, nullptr, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
-    constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) + 16;
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_march_kernel<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (*blocks_per_cu == 0) {
+        const void* fn;
+        if constexpr (std::is_same<K1, std::nullptr_t>::value) fn = (const void*)kernel;
+        else fn = (const void*)kernel_one;
+        TOPO_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nblk, (const void*)tpi_march_kernel<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>, NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
+        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, fn, threads, lds));
+        *blocks_per_cu = nblk < 1 ? 1 : (cap > 0 && nblk > cap ? cap : nblk);
     }
     WaveParts ps;
     int tiles_x = 0;
     long ntiles = 0;
+    TOPO_TRY(make_parts(b, a, tile_h, strip_w, want_defer, want_sums, &ps, &tiles_x, &ntiles, map_th, map_tw));
+    // persistent blocks fill the chip (whole XCD rounds: the tile list is cut into XCD-contiguous runs); launches of one
+    // geometry get the same grid, hence the same runs
+    const long grid = march_grid(c, *blocks_per_cu, ntiles);
+    TOPO_TRY(prepare(ps, grid));
+    deal_parts(&ps, tiles_x, grid, *blocks_per_cu);
+    return launch_parts(kernel_one, kernel, grid, threads, lds, ps, tiles_x);
+}
+
+template <int SIZE, int TH, int NWAVES, bool OUT_TPI, bool OUT_SUM, bool ALLOW_FRAC = false>
+int launch_march(const Block& b, float* tpi_out, bool scaled = false) {
+    WaveArgs a = wave_args(b, tpi_out, nullptr);
+    constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) + 16;
+    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
+    static int blocks_per_cu = 0;
     a.scaled = ALLOW_FRAC && scaled ? 1 : 0;
     a.report = ALLOW_FRAC && scaled ? dem_memo_report(b) : nullptr;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, true, OUT_SUM && a.scaled == 0, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(tpi_march_kernel<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>, tpi_march_kernel_parts<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>, grid, NWAVES * 64, lds, ps, tiles_x);
+    return launch_tiles(tpi_march_kernel<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>, tpi_march_kernel_parts<SIZE, TH, NWAVES, OUT_TPI, OUT_SUM, ALLOW_FRAC>,
+                        &blocks_per_cu, NWAVES * 64, lds, 0, b, a, TH, Geo<SIZE>::TILE_W, true, OUT_SUM && a.scaled == 0);
 }
 
 // the first of the three marching passes of STD on fractional elevations: sums of trunc(x) for every tile, TPI of the whole-metre ones
 template <int SIZE, int TH, int NWAVES, bool OUT_TPI>
 int launch_march_sums(const Block& b, float* tpi_out) {
-    using G = Geo<SIZE>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, nullptr, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
     constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) + 16;
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_march_sums_kernel<SIZE, TH, NWAVES, OUT_TPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)tpi_march_sums_kernel<SIZE, TH, NWAVES, OUT_TPI>, NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, true, true, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(nullptr, tpi_march_sums_kernel<SIZE, TH, NWAVES, OUT_TPI>, grid, NWAVES * 64, lds, ps, tiles_x);
+    return launch_tiles(nullptr, tpi_march_sums_kernel<SIZE, TH, NWAVES, OUT_TPI>, &blocks_per_cu, NWAVES * 64, lds, 0, b,
+                        wave_args(b, tpi_out, nullptr), TH, Geo<SIZE>::TILE_W, true, true);
 }
 
 // ---- TPI on tiles with fractional elevations: the fraction pass ---------------------------------
@@ -1578,28 +1587,11 @@ __global__ __launch_bounds__(NWAVES * 64) void tpi_fraction_march_kernel(WavePar
 
 template <int SIZE, int TH, int NWAVES, bool WANT_STD = false>
 int launch_fraction_march(const Block& b, float* tpi_out, float* std_out = nullptr) {
-    using G = Geo<SIZE>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
     constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) + 16 + (WANT_STD ? (size_t)NWAVES * ROWW * sizeof(int) : 0);
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_fraction_march_kernel<SIZE, TH, NWAVES, WANT_STD>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nblk, (const void*)tpi_fraction_march_kernel<SIZE, TH, NWAVES, WANT_STD>, NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, true, true, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);  // the same grid, hence the same runs, as launch_march
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(nullptr, tpi_fraction_march_kernel<SIZE, TH, NWAVES, WANT_STD>, grid, NWAVES * 64, lds, ps, tiles_x);
+    return launch_tiles(nullptr, tpi_fraction_march_kernel<SIZE, TH, NWAVES, WANT_STD>, &blocks_per_cu, NWAVES * 64, lds, 0, b,
+                        wave_args(b, tpi_out, std_out), TH, Geo<SIZE>::TILE_W, true, true);
 }
 
 // ---- TPI on tiles with fractional elevations: the scaled one-chain route (round 4) -----------------------------------
@@ -1840,30 +1832,15 @@ __global__ __launch_bounds__(NWAVES * 64) void tpi_scaled_march_kernel(WaveParts
 template <int SIZE, int TH, int NWAVES, bool TAKE_ALL = false>
 int launch_scaled_march(const Block& b, float* tpi_out) {
     using G = Geo<SIZE>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, nullptr, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
+    WaveArgs a = wave_args(b, tpi_out, nullptr);
     a.scaled = 1;
     a.unit = scaled_unit(G::T.taps);
     a.report = TAKE_ALL ? dem_memo_report(b) : nullptr;
     constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) + 16 + 388 * sizeof(int);
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)tpi_scaled_march_kernel<SIZE, TH, NWAVES, TAKE_ALL>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nblk, (const void*)tpi_scaled_march_kernel<SIZE, TH, NWAVES, TAKE_ALL>, NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, true, false, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);  // the same grid, hence the same runs, as launch_march
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(nullptr, tpi_scaled_march_kernel<SIZE, TH, NWAVES, TAKE_ALL>, grid, NWAVES * 64, lds, ps, tiles_x);
+    return launch_tiles(nullptr, tpi_scaled_march_kernel<SIZE, TH, NWAVES, TAKE_ALL>, &blocks_per_cu, NWAVES * 64, lds, 0, b, a, TH,
+                        G::TILE_W, true, false);
 }
 
 // ---- STD on tiles of whole metres: the second marching kernel ------------------------------------
@@ -2155,29 +2132,12 @@ __global__ __launch_bounds__(NWAVES * 64) void std_march_kernel(WaveParts ps, in
 
 template <int SIZE, int TH, int NWAVES, bool FRAC_STORE = false>
 int launch_std_march(const Block& b, float* std_out) {
-    using G = Geo<SIZE>;
-    Context& c = ctx();
-    WaveArgs a{b.in, nullptr, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
     constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(int) +
                            (size_t)((TH * (SIZE + 1) + 7) & ~7) * sizeof(unsigned short) + 16;
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)std_march_kernel<SIZE, TH, NWAVES, FRAC_STORE>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)std_march_kernel<SIZE, TH, NWAVES, FRAC_STORE>,
-                                                              NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, true, true, &ps, &tiles_x, &ntiles));
-    const long grid = march_grid(c, blocks_per_cu, ntiles);  // the same grid, hence the same runs, as launch_march
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);
-    return launch_parts(nullptr, std_march_kernel<SIZE, TH, NWAVES, FRAC_STORE>, grid, NWAVES * 64, lds, ps, tiles_x);
+    return launch_tiles(nullptr, std_march_kernel<SIZE, TH, NWAVES, FRAC_STORE>, &blocks_per_cu, NWAVES * 64, lds, 0, b,
+                        wave_args(b, nullptr, std_out), TH, Geo<SIZE>::TILE_W, true, true);
 }
 
 // only_deferred: process the tiles a preceding launch_march of the same geometry marked.
@@ -2185,35 +2145,21 @@ int launch_std_march(const Block& b, float* std_out) {
 template <int SIZE, int TH, int NWAVES, bool WANT_TPI, bool WANT_STD>
 int launch_wave(const Block& b, float* tpi_out, float* std_out, bool only_deferred = false, int map_th = 0,
                 int map_tw = 0) {
-    using G = Geo<SIZE>;
-    Context& c = ctx();
-    WaveArgs a{b.in, tpi_out, std_out, b.in_rows, b.in_row0, b.gny, b.nx, b.out_row0, b.out_rows,
-               nullptr, nullptr, nullptr, 0, 0};
     constexpr size_t lds = (size_t)((TH + SIZE) + NWAVES) * ROWW * sizeof(float) +
                            (size_t)((TH * (SIZE + 1) + 7) & ~7) * sizeof(unsigned short) + 16;
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     static_assert(SIZE * SIZE < 65536, "tap counts must fit the 16-bit border table");
     static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        TOPO_HIP(hipFuncSetAttribute((const void*)disc_wave_kernel<SIZE, TH, NWAVES, WANT_TPI, WANT_STD>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nblk = 0;
-        TOPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nblk, (const void*)disc_wave_kernel<SIZE, TH, NWAVES, WANT_TPI, WANT_STD>, NWAVES * 64, lds));
-        blocks_per_cu = nblk < 1 ? 1 : nblk;
-    }
-    WaveParts ps;
-    int tiles_x = 0;
-    long ntiles = 0;
-    TOPO_TRY(make_parts(b, a, TH, G::TILE_W, only_deferred, false, &ps, &tiles_x, &ntiles, only_deferred ? map_th : 0,
-                        only_deferred ? map_tw : 0));
-    // persistent blocks fill the chip (whole XCD rounds: the tile list is cut into XCD-contiguous runs)
-    const long grid = march_grid(c, blocks_per_cu, ntiles);
-    void* scratch = nullptr;
-    TOPO_TRY(workspace(2, (size_t)grid * kScratchPlanes * TH * ROWW * sizeof(uint32_t), &scratch));
-    for (int k = 0; k < kMaxParts; ++k) ps.a[k].scratch = (uint32_t*)scratch;
-    deal_parts(&ps, tiles_x, grid, blocks_per_cu);  // (this kernel deals its tiles round-robin: only the shifts matter)
-    return launch_parts(nullptr, disc_wave_kernel<SIZE, TH, NWAVES, WANT_TPI, WANT_STD>, grid, NWAVES * 64, lds, ps, tiles_x);
+    const auto scratch_planes = [](WaveParts& ps, long grid) -> int {  // the blocks' per-row sums between the kernel's passes
+        void* scratch = nullptr;
+        TOPO_TRY(workspace(2, (size_t)grid * kScratchPlanes * TH * ROWW * sizeof(uint32_t), &scratch));
+        for (int k = 0; k < kMaxParts; ++k) ps.a[k].scratch = (uint32_t*)scratch;
+        return TOPO_AMD_OK;
+    };
+    // (this kernel deals its tiles round-robin: of launch_tiles' dealing only the shifts matter)
+    return launch_tiles(nullptr, disc_wave_kernel<SIZE, TH, NWAVES, WANT_TPI, WANT_STD>, &blocks_per_cu, NWAVES * 64, lds, 0, b,
+                        wave_args(b, tpi_out, std_out), TH, Geo<SIZE>::TILE_W, only_deferred, false, only_deferred ? map_th : 0,
+                        only_deferred ? map_tw : 0, scratch_planes);
 }
 
 }  // namespace
@@ -2236,36 +2182,43 @@ constexpr int tile_rows(int size, int nwaves, int cap) {
     return th;
 }
 
-// Which discs take the marching kernels.  Measured on a 32768^2 DEM of whole metres
-// (profiles/r01_std_crossover.txt): for STD / TPI+STD the marching pair wins
-// from 31 px (2 %) to 67 px (11 %) and loses below (three planes of traffic in one general kernel
-// against five) and wherever LDS no longer holds the full 60-row tile (101 px: 36-row tiles, 46 ms
-// against 31 ms).  (The lower bounds were environment switches until round 5; constants now.)
+// ---- Which disc size takes which kernels: one predicate per route (launch_tpi_any, launch_std_any) ---------------
+// LDS holds the tile height the marching kernels were tuned for (up to 77 px; 48 rows at 79 px, 36 at 101).
+constexpr bool march_full_tile(int size) { return tile_rows(size, 12, 60) == 60; }
+// STD / TPI + STD by the one-pass ring kernel (disc_ring_impl.hpp), wherever its ring fits: 5 ... 67 px.  Same-box
+// A/B on the 32768^2 bench DEM (tools/std_time.py, profiles/r02_std_ring.txt), ring kernel against what it replaces:
+// STD 7 px 3.10 / 5.67 ms, 17 px 3.77 / 6.40, 31 px 5.28 / 7.89, 45 px 6.76 / 9.70, 65 px 9.37 / 12.78, 67 px 10.33 /
+// 13.61; TPI + STD 67 px 10.86 / 14.22.  Identical bits (CRC-32 of both planes, whole metres and fractional DEM).
+constexpr bool std_takes_ring(int size) { return std_ring_fits(size); }
+// ... in front of it on a raster of whole metres, the 512-column build: TPI + STD up to 13 px, STD alone at 5 and 7 px
+// (the measurements: launch_std_any)
+constexpr bool std_takes_spec_wide(int size, bool want_tpi) { return std_spec_wide_fits(size) && (want_tpi || size <= 7); }
+// ... and in front of both on a raster of mostly fractional elevations, the three marching passes: the sizes whose ring has no
+// room for the third image, 43 ... 67 px
+constexpr bool std_takes_three_marches(int size) { return std_ring_fits(size) && !std_ring_both_fits(size) && march_full_tile(size); }
+// STD / TPI + STD by the marching pair where the ring does not fit: 69 ... 77 px.  Measured on a 32768^2 DEM of whole metres
+// (profiles/r01_std_crossover.txt): the marching pair wins from 31 px (2 %) to 67 px (11 %) and loses below (three planes of
+// traffic in one general kernel against five) and wherever LDS no longer holds the full 60-row tile (101 px: 36-row tiles,
+// 46 ms against 31 ms).  Every other size - 3 px, and from 79 px - takes the general kernel alone.
+constexpr bool std_takes_march_pair(int size) { return !std_ring_fits(size) && size >= 31 && march_full_tile(size); }
+// TPI alone by the ring build (disc_ring_impl.hpp) instead of tpi_march_kernel (both give the same bits): 5 ... 17 px.
+// Measured on the 32768^2 bench DEM (profiles/r02_tpi_ring.txt): 2.03-2.06 ms against 2.31-2.37 ms for 5 ... 11 px, level at
+// 13-17 px, 4.6 ms against 4.4 ms at 67 px.  Round 3: the ring sizes go up to 17 px, because with fractional elevations the
+// two-image pass (kRingBoth) halves the time there (7 px 5.36 -> 2.48 ms, 13 px 5.82 -> 3.60, 17 px 6.00 -> 3.79,
+// profiles/r03_tpi_ring_both.txt) while whole metres cost the same to 15 px and 5 % more at 17 (2.43 against 2.32 ms).
+constexpr bool tpi_takes_ring(int size) { return ring_both_fits(size) && size <= 17; }
+// TPI alone, the other sizes: from 17 px the tiles with fractional elevations get a marching pass of their own (the scaled
+// one, or the exact pair) instead of the general kernel, whose two passes over one tile beat two marching kernels on small
+// discs.  (With the ring in front up to 17 px: 3 px takes one marching kernel, 19 px and more take two.)
+constexpr bool tpi_takes_fraction_pass(int size) { return size >= 17; }
+// TPI alone by the wide ring (disc_ring_wide_impl.hpp: 6 columns per lane, staging waves apart), in front of the scaled pass
+// and the general kernel: 67 px, whole-metre raster class, single-block calls.
+constexpr bool tpi_takes_wide_ring(int size) { return tpi_wide_ring_fits(size) && size == 67; }
+
 inline int env_int(const char* name, int fallback) {
     const char* e = std::getenv(name);
     return e ? std::atoi(e) : fallback;
 }
-constexpr int std_march_min_size() { return 31; }
-constexpr int tpi_march_min_size() { return 1; }
-// Disc size from which TPI on tiles with fractional elevations takes the two marching passes
-// (sum of trunc(x), then sum of the fractional parts) instead of the general kernel.
-// Disc size from which TPI takes the ring build (disc_ring_impl.hpp) instead of tpi_march_kernel (both give the same bits).
-// Measured on the 32768^2 bench DEM (profiles/r02_tpi_ring.txt): 2.03-2.06 ms against
-// 2.31-2.37 ms for 5 ... 11 px, level at 13-17 px, 4.6 ms against 4.4 ms at 67 px.  Round 3: the ring sizes go up
-// to 17 px, because with fractional elevations the two-image pass (kRingBoth) halves the time there (7 px 5.36 ->
-// 2.48 ms, 13 px 5.82 -> 3.60, 17 px 6.00 -> 3.79, profiles/r03_tpi_ring_both.txt) while whole metres cost the
-// same to 15 px and 5 % more at 17 (2.43 against 2.32 ms).
-constexpr int tpi_ring_min_size() { return 5; }
-// Disc size from which STD / TPI + STD take the one-pass ring kernel.  Same-box
-// A/B on the 32768^2 bench DEM (tools/std_time.py, profiles/r02_std_ring.txt), ring kernel against what it replaces:
-// STD 7 px 3.10 / 5.67 ms, 17 px 3.77 / 6.40, 31 px 5.28 / 7.89, 45 px 6.76 / 9.70, 65 px 9.37 / 12.78, 67 px 10.33 /
-// 13.61; TPI + STD 67 px 10.86 / 14.22.  Identical bits (CRC-32 of both planes, whole metres and fractional DEM).
-constexpr int std_ring_min_size() { return 5; }
-constexpr int tpi_ring_max_size() { return 17; }
-// Disc sizes TPI alone takes the wide ring for (disc_ring_wide_impl.hpp: 6 columns per lane, staging waves apart), in front of
-// the scaled pass and the general kernel: whole-metre raster class, single-block calls.
-constexpr int tpi_wide_min_size() { return 67; }
-constexpr int tpi_wide_max_size() { return 67; }
 // (lab switch: TOPO_AMD_TPI_WIDE_RING=0 keeps the marching kernel, for the A/B)
 inline bool tpi_wide_ring() {
     static const int v = env_int("TOPO_AMD_TPI_WIDE_RING", 1);
@@ -2277,161 +2230,148 @@ inline bool tpi_fraction_scaled() {
     static const int v = env_int("TOPO_AMD_TPI_FRACTION_EXACT", 0);
     return v == 0;
 }
-constexpr int tpi_fraction_min_size() { return 17; }
 // (lab switch: TOPO_AMD_STD_SPEC_WIDE=0 keeps the 256-column strips at 5 and 7 px)
 inline bool std_spec_wide() {
     static const int v = env_int("TOPO_AMD_STD_SPEC_WIDE", 1);
     return v != 0;
 }
 
+// what topo_amd_disc_route reports: the first kernel over the whole-metre tiles, its tile height, the followers queued
+constexpr int disc_word(int wanted, int first, int th, int followers) { return kDiscWave | wanted | first | (th << kDiscTileShift) | followers; }
+
+// TPI alone.  The first kernels take the tiles of whole metres, the general kernel (12 waves, tiles of TH rows) the tiles
+// they left: none on a DEM of whole metres.
 template <int SIZE>
-int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
-    constexpr int TH8 = tile_rows(SIZE, 8, 64), TH12 = tile_rows(SIZE, 12, 60);
-    // The marching kernels take the tiles of whole metres, the general kernel the tiles they left
-    // (none on a DEM of whole metres; all of them on one with fractional elevations).
-    constexpr bool kFullTile = TH12 == 60;  // LDS holds the tile height the marching kernels were tuned for
-    // what topo_amd_disc_route reports: the first kernel over the whole-metre tiles, its tile height, the followers queued
-    const int wanted = kDiscWave | (tpi_out ? kDiscTpi : 0) | (std_out ? kDiscStd : 0);
-    const auto route = [wanted](int first, int th, int followers) { return wanted | first | (th << kDiscTileShift) | followers; };
-    if constexpr (std_ring_fits(SIZE) && !std_ring_both_fits(SIZE) && kFullTile) {
-        // STD (and TPI + STD) on a raster of mostly fractional elevations, discs of 43 ... 67 px (below, the ring kernel has
-        // a three-image second pass; here three images do not fit LDS and every tile used to end with the general kernel's
-        // three staging passes: 20 ms at 67 px on 32768^2).  Three marching passes instead, each carrying its window down
-        // the strips: the sums of trunc(x) (and TPI of the whole-metre tiles), the sums of (trunc(x) - c)^2 (and STD of the
-        // whole-metre tiles), the sums of the fractional parts with the finalisation of the rest.  Exact sums and the
-        // general kernel's expressions: the same bits.  Which route runs first is a matter of time only; it is taken from
-        // the share of fractional samples in the raster class.
-        if (std_out && current_class().frac_share > 0.5f) {
-            if (tpi_out) TOPO_TRY((launch_march_sums<SIZE, TH12, 12, true>(b, tpi_out)));
-            else TOPO_TRY((launch_march_sums<SIZE, TH12, 12, false>(b, nullptr)));
-            TOPO_TRY((launch_std_march<SIZE, TH12, 12, true>(b, std_out)));
-            TOPO_TRY((launch_fraction_march<SIZE, TH12, 12, true>(b, tpi_out, std_out)));
-            const int word = route(kDiscFirstSums, TH12, kDiscStdMarch | kDiscFracMarch | kDiscDeferred);
-            if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12), word);
-            return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12), word);
-        }
-    }
-    if constexpr (std_ring_fits(SIZE)) {
-        if (std_out && SIZE >= std_ring_min_size()) {
-            // one staging pass: u and u^2 rings side by side (disc_ring_impl.hpp), then the general kernel over
-            // the tiles it marked (its map has this kernel's strips and rows of 60)
-            // (the tiles at the DEM's border are the ring kernel's own: the padding's zeros are staged as samples, and such a
-            // window is the general kernel's only when its highest sample passes 2 lim32 - disc_ring_impl.hpp)
-            if constexpr (std_spec_wide_fits(SIZE)) {
-                // A raster of whole metres (the raster class: TIME only - every route is exact): 512-column strips, 8 columns per
-                // lane; a tile with fractional samples is the general kernel's then (no second pass on this map).  With row
-                // segments of 2 KiB the two-plane call has no slow mode (tools/two_plane_pairs.py: 2.84 - 3.12 ms for all 30 pairs
-                // of six planes at 7 px, where the 256-column strips run at 2.98 with one plane and 3.85 with the others), and
-                // STD alone gains 2 - 6 % at 5 and 7 px.  From 9 px the ring holds one row per chain wave only and STD alone
-                // loses (9 px 2.37 -> 3.11 ms) while TPI + STD still wins over its usual slow mode up to 13 px (3.60 -> 3.06,
-                // 3.57 -> 3.23): profiles/r05_std_wide_ab.txt.
-                // (STD alone on a small raster keeps the 256-column strips: 8192^2 has 18 strips of 480 columns for 17.07 and 12 tiles
-                // per block where the narrow form, two blocks per CU, has 17.7: 0.148 against 0.161 ms)
-                const bool big = (long)b.nx * b.out_rows >= (1L << 27);  // (a 4096-row shard of a 32768-column DEM included)
-                if (current_class().frac_share == 0.0f && std_spec_wide() && (tpi_out != nullptr || (SIZE <= 7 && big))) {
-                    if (tpi_out) TOPO_TRY((launch_std_ring_spec<SIZE, true, false, 8>(b, tpi_out, std_out)));
-                    else TOPO_TRY((launch_std_ring_spec<SIZE, false, false, 8>(b, nullptr, std_out)));
-                    const int word = route(kDiscFirstSpec8, StdRingCfg<SIZE>::TH, kDiscDeferred);
-                    if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W), word);
-                    return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH, RGeo<SIZE, 8>::TILE_W), word);
-                }
+int launch_tpi_any(const Block& b, float* tpi_out) {
+    constexpr int TH = tile_rows(SIZE, 12, 60);
+    const auto route = [](int first, int th, int followers) { return disc_word(kDiscTpi, first, th, followers); };
+    // the last launch of every route: the general kernel over the tiles marked in the map of map_th x map_tw (0: its own)
+    const auto deferred = [&](int map_th, int map_tw, int word) {
+        return note_disc_if_ok(launch_wave<SIZE, TH, 12, true, false>(b, tpi_out, nullptr, true, map_th, map_tw), word);
+    };
+    if constexpr (tpi_takes_ring(SIZE)) {
+        using RC = RingCfg<SIZE, 8>;
+        // whole-metre tiles in the first pass; tiles with fractional elevations in ONE second pass with two rings
+        // (trunc(x) and the fractional parts); what neither could take in the general kernel.  On the 32768^2 bench
+        // DEM with fractional elevations: 7 px 5.36 -> 2.48 ms, 17 px 5.31 -> 3.79 ms (profiles/r03_tpi_ring_both.txt)
+        TOPO_TRY((launch_ring<SIZE, 8, kRingMark>(b, tpi_out)));
+        TOPO_TRY((launch_ring<SIZE, 8, kRingBoth>(b, tpi_out)));
+        return deferred(RC::TH, RGeo<SIZE, 8>::TILE_W, route(kDiscFirstRing, RC::TH, kDiscFracRingBoth | kDiscDeferred));
+    } else if constexpr (!tpi_takes_fraction_pass(SIZE)) {
+        TOPO_TRY((launch_march<SIZE, TH, 12, true, false, false>(b, tpi_out)));
+        return deferred(0, 0, route(kDiscFirstMarch, TH, kDiscDeferred));
+    } else {
+        // whole-metre tiles are finished by the first marching kernel; tiles with fractional elevations get their sum
+        // in a second one; the general kernel takes what neither could (non-finite or absurd samples)
+        if constexpr (tpi_takes_wide_ring(SIZE)) {
+            // whole metres, one block: the wide ring computes the phases whose windows hold whole metres and marks the marching
+            // geometry's tiles of the others (fractional, non-finite or absurd samples) for the scaled pass, which leaves what it
+            // cannot take to the general kernel - the marching route's two followers on the marching route's map
+            const bool one_block = b.out_row0 == 0 && b.out_rows == b.gny && ctx().seams.n == 0;
+            if (tpi_wide_ring() && tpi_fraction_scaled() && one_block && current_class().frac_share == 0.0f &&
+                !dem_memo_mostly_fractional(b)) {
+                TOPO_TRY((launch_ring_wide<SIZE>(b, tpi_out, TH, Geo<SIZE>::TILE_W)));
+                note_tpi_route(1);
+                TOPO_TRY((launch_scaled_march<SIZE, TH, 12>(b, tpi_out)));
+                return deferred(0, 0, route(kDiscFirstWide, WideCfg<SIZE>::TH, kDiscScaledMarch | kDiscDeferred | kDiscWideRing));
             }
-            if constexpr (std_ring_spec(SIZE)) {  // the small discs: staging waves apart from chain waves
-                if (tpi_out) TOPO_TRY((launch_std_ring_spec<SIZE, true>(b, tpi_out, std_out)));
-                else TOPO_TRY((launch_std_ring_spec<SIZE, false>(b, nullptr, std_out)));
-            } else {
-                if (tpi_out) TOPO_TRY((launch_std_ring<SIZE, true>(b, tpi_out, std_out)));
-                else TOPO_TRY((launch_std_ring<SIZE, false>(b, nullptr, std_out)));
-            }
-            if constexpr (std_ring_both_fits(SIZE)) {
-                // tiles with fractional elevations: one more pass of the ring kernel with a third image (the
-                // fractional parts) instead of the general kernel's three staging passes
-                if constexpr (std_spec_both_fits(SIZE)) {  // (up to 21 px: in the form with staging waves apart from chain waves)
-                    if (tpi_out) TOPO_TRY((launch_std_ring_spec<SIZE, true, true>(b, tpi_out, std_out)));
-                    else TOPO_TRY((launch_std_ring_spec<SIZE, false, true>(b, nullptr, std_out)));
-                } else {
-                    if (tpi_out) TOPO_TRY((launch_std_ring<SIZE, true, kStdBoth>(b, tpi_out, std_out)));
-                    else TOPO_TRY((launch_std_ring<SIZE, false, kStdBoth>(b, nullptr, std_out)));
-                }
-            }
-            const int word = route(std_ring_spec(SIZE) ? kDiscFirstSpec4 : kDiscFirstStdRing, StdRingCfg<SIZE>::TH,
-                                   (!std_ring_both_fits(SIZE) ? 0 : std_spec_both_fits(SIZE) ? kDiscFracSpecBoth : kDiscFracStdRingBoth) | kDiscDeferred);
-            if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH), word);
-            return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, StdRingCfg<SIZE>::TH), word);
         }
-    }
-    if (std_out && (SIZE < std_march_min_size() || !kFullTile)) {
-        // small discs: one general kernel (two passes per tile, the second one out of L2) moves three
-        // planes where the marching pair moves five, and the chains are too short to matter
-        if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH8, 0));
-        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH8, 0));
-    }
-    if (std_out) {
-        // sum x (and TPI) marching, then sum u^2 -> STD marching over the same runs, then the
-        // 8-wave general kernel (tiles of TH8 rows) over whatever overlaps a marked tile
-        if (tpi_out) {
-            TOPO_TRY((launch_march<SIZE, TH12, 12, true, true>(b, tpi_out)));
-        } else {
-            TOPO_TRY((launch_march<SIZE, TH12, 12, false, true>(b, nullptr)));
+        if (!tpi_fraction_scaled()) {
+            // the exact pair: the sum of trunc(x), then the sum of the fractional parts in units of 2^-16 m
+            TOPO_TRY((launch_march<SIZE, TH, 12, true, true, true>(b, tpi_out)));
+            TOPO_TRY((launch_fraction_march<SIZE, TH, 12>(b, tpi_out)));
+            return deferred(0, 0, route(kDiscFirstMarch, TH, kDiscFracMarch | kDiscDeferred));
         }
-        TOPO_TRY((launch_std_march<SIZE, TH12, 12>(b, std_out)));
-        const int word = route(kDiscFirstMarch, TH12, kDiscStdMarch | kDiscDeferred);
-        if (tpi_out) return note_disc_if_ok(launch_wave<SIZE, TH8, 8, true, true>(b, tpi_out, std_out, true, TH12), word);
-        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, false, true>(b, tpi_out, std_out, true, TH12), word);
-    }
-    if (SIZE < tpi_march_min_size()) return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH12, 0));
-    // TPI alone: whole-metre tiles are finished by the first marching kernel; tiles with fractional
-    // elevations get their exact sum of trunc(x) there and the sum of the fractional parts in the
-    // second; the general kernel takes what neither could (non-finite or absurd samples)
-    // the ring build (disc_ring_impl.hpp) is compiled for the sizes it wins at and for the headline sizes (A/B)
-    constexpr bool kRing = ring_both_fits(SIZE) && SIZE <= 17;
-    if constexpr (kRing) {
-        if (SIZE >= tpi_ring_min_size() && SIZE <= tpi_ring_max_size()) {
-            using RC = RingCfg<SIZE, 8>;
-            constexpr int map_tw = RGeo<SIZE, 8>::TILE_W;
-            // whole-metre tiles in the first pass; tiles with fractional elevations in ONE second pass with two rings
-            // (trunc(x) and the fractional parts); what neither could take in the general kernel.  On the 32768^2 bench
-            // DEM with fractional elevations: 7 px 5.36 -> 2.48 ms, 17 px 5.31 -> 3.79 ms (profiles/r03_tpi_ring_both.txt)
-            TOPO_TRY((launch_ring<SIZE, 8, kRingMark>(b, tpi_out)));
-            TOPO_TRY((launch_ring<SIZE, 8, kRingBoth>(b, tpi_out)));
-            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true, RC::TH, map_tw),
-                                   route(kDiscFirstRing, RC::TH, kDiscFracRingBoth | kDiscDeferred));
-        }
-    }
-    if (SIZE < tpi_fraction_min_size()) {
-        // small discs: the general kernel's two passes over one tile beat two marching kernels
-        TOPO_TRY((launch_march<SIZE, TH12, 12, true, false, false>(b, tpi_out)));
-        return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscDeferred));
-    }
-    if constexpr (tpi_wide_ring_fits(SIZE) && SIZE >= tpi_wide_min_size() && SIZE <= tpi_wide_max_size()) {
-        // whole metres, one block: the wide ring computes the phases whose windows hold whole metres and marks the marching
-        // geometry's tiles of the others (fractional, non-finite or absurd samples) for the scaled pass, which leaves what it
-        // cannot take to the general kernel - the marching route's two followers on the marching route's map
-        const bool one_block = b.out_row0 == 0 && b.out_rows == b.gny && ctx().seams.n == 0;
-        if (tpi_wide_ring() && tpi_fraction_scaled() && one_block && current_class().frac_share == 0.0f &&
-            !dem_memo_mostly_fractional(b)) {
-            TOPO_TRY((launch_ring_wide<SIZE>(b, tpi_out, TH12, Geo<SIZE>::TILE_W)));
-            note_tpi_route(1);
-            TOPO_TRY((launch_scaled_march<SIZE, TH12, 12>(b, tpi_out)));
-            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true),
-                                   route(kDiscFirstWide, WideCfg<SIZE>::TH, kDiscScaledMarch | kDiscDeferred | kDiscWideRing));
-        }
-    }
-    if (tpi_fraction_scaled()) {
         // fractional tiles: one chain on x in units of 2^-8 m (tpi_scaled_march_kernel: <= 1.95 mm, see there)
         // (what the last call on this block reported, or - a block seen for the first time, a host-buffer call - what the
         // raster class says: the scaled build takes every tile)
         if (dem_memo_mostly_fractional(b) || current_class().frac_share > 0.5f) {
-            TOPO_TRY((launch_scaled_march<SIZE, TH12, 12, true>(b, tpi_out)));
-            return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstScaledAll, TH12, kDiscDeferred));
+            TOPO_TRY((launch_scaled_march<SIZE, TH, 12, true>(b, tpi_out)));
+            return deferred(0, 0, route(kDiscFirstScaledAll, TH, kDiscDeferred));
         }
-        TOPO_TRY((launch_march<SIZE, TH12, 12, true, true, true>(b, tpi_out, true)));
-        TOPO_TRY((launch_scaled_march<SIZE, TH12, 12>(b, tpi_out)));
-        return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscScaledMarch | kDiscDeferred));
+        TOPO_TRY((launch_march<SIZE, TH, 12, true, true, true>(b, tpi_out, true)));
+        TOPO_TRY((launch_scaled_march<SIZE, TH, 12>(b, tpi_out)));
+        return deferred(0, 0, route(kDiscFirstMarch, TH, kDiscScaledMarch | kDiscDeferred));
     }
-    TOPO_TRY((launch_march<SIZE, TH12, 12, true, true, true>(b, tpi_out)));
-    TOPO_TRY((launch_fraction_march<SIZE, TH12, 12>(b, tpi_out)));
-    return note_disc_if_ok(launch_wave<SIZE, TH12, 12, true, false>(b, tpi_out, std_out, true), route(kDiscFirstMarch, TH12, kDiscFracMarch | kDiscDeferred));
+}
+
+// STD (tpi_out == nullptr) and TPI + STD.  As above with the 8-wave general kernel (tiles of TH8 rows), which takes whatever
+// overlaps a tile the first kernels marked.
+template <int SIZE, bool WANT_TPI>
+int launch_std_any(const Block& b, float* tpi_out, float* std_out) {
+    constexpr int TH8 = tile_rows(SIZE, 8, 64), TH12 = tile_rows(SIZE, 12, 60);
+    const auto route = [](int first, int th, int followers) { return disc_word((WANT_TPI ? kDiscTpi : 0) | kDiscStd, first, th, followers); };
+    const auto deferred = [&](int map_th, int map_tw, int word) {
+        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, WANT_TPI, true>(b, tpi_out, std_out, true, map_th, map_tw), word);
+    };
+    if constexpr (std_takes_three_marches(SIZE)) {
+        // A raster of mostly fractional elevations, discs of 43 ... 67 px (below, the ring kernel has a three-image second
+        // pass; here three images do not fit LDS and every tile used to end with the general kernel's three staging
+        // passes: 20 ms at 67 px on 32768^2).  Three marching passes instead, each carrying its window down the strips: the
+        // sums of trunc(x) (and TPI of the whole-metre tiles), the sums of (trunc(x) - c)^2 (and STD of the whole-metre
+        // tiles), the sums of the fractional parts with the finalisation of the rest.  Exact sums and the general kernel's
+        // expressions: the same bits.  Which route runs first is a matter of time only; it is taken from the share of
+        // fractional samples in the raster class.
+        if (current_class().frac_share > 0.5f) {
+            TOPO_TRY((launch_march_sums<SIZE, TH12, 12, WANT_TPI>(b, tpi_out)));
+            TOPO_TRY((launch_std_march<SIZE, TH12, 12, true>(b, std_out)));
+            TOPO_TRY((launch_fraction_march<SIZE, TH12, 12, true>(b, tpi_out, std_out)));
+            return deferred(TH12, 0, route(kDiscFirstSums, TH12, kDiscStdMarch | kDiscFracMarch | kDiscDeferred));
+        }
+    }
+    if constexpr (std_takes_ring(SIZE)) {
+        // one staging pass: u and u^2 rings side by side (disc_ring_impl.hpp), then the general kernel over
+        // the tiles it marked (its map has this kernel's strips and rows of 60)
+        // (the tiles at the DEM's border are the ring kernel's own: the padding's zeros are staged as samples, and such a
+        // window is the general kernel's only when its highest sample passes 2 lim32 - disc_ring_impl.hpp)
+        constexpr int RTH = StdRingCfg<SIZE>::TH;
+        if constexpr (std_takes_spec_wide(SIZE, WANT_TPI)) {
+            // A raster of whole metres (the raster class: TIME only - every route is exact): 512-column strips, 8 columns per
+            // lane; a tile with fractional samples is the general kernel's then (no second pass on this map).  With row
+            // segments of 2 KiB the two-plane call has no slow mode (tools/two_plane_pairs.py: 2.84 - 3.12 ms for all 30 pairs
+            // of six planes at 7 px, where the 256-column strips run at 2.98 with one plane and 3.85 with the others), and
+            // STD alone gains 2 - 6 % at 5 and 7 px.  From 9 px the ring holds one row per chain wave only and STD alone
+            // loses (9 px 2.37 -> 3.11 ms) while TPI + STD still wins over its usual slow mode up to 13 px (3.60 -> 3.06,
+            // 3.57 -> 3.23): profiles/r05_std_wide_ab.txt.
+            // (STD alone on a small raster keeps the 256-column strips: 8192^2 has 18 strips of 480 columns for 17.07 and 12 tiles
+            // per block where the narrow form, two blocks per CU, has 17.7: 0.148 against 0.161 ms)
+            const bool big = (long)b.nx * b.out_rows >= (1L << 27);  // (a 4096-row shard of a 32768-column DEM included)
+            if (current_class().frac_share == 0.0f && std_spec_wide() && (WANT_TPI || big)) {
+                TOPO_TRY((launch_std_ring_spec<SIZE, WANT_TPI, false, 8>(b, tpi_out, std_out)));
+                return deferred(RTH, RGeo<SIZE, 8>::TILE_W, route(kDiscFirstSpec8, RTH, kDiscDeferred));
+            }
+        }
+        if constexpr (std_ring_spec(SIZE)) {  // the small discs: staging waves apart from chain waves
+            TOPO_TRY((launch_std_ring_spec<SIZE, WANT_TPI>(b, tpi_out, std_out)));
+        } else {
+            TOPO_TRY((launch_std_ring<SIZE, WANT_TPI>(b, tpi_out, std_out)));
+        }
+        // tiles with fractional elevations: one more pass of the ring kernel with a third image (the fractional parts)
+        // instead of the general kernel's three staging passes
+        if constexpr (std_spec_both_fits(SIZE)) {  // (up to 21 px: in the form with staging waves apart from chain waves)
+            TOPO_TRY((launch_std_ring_spec<SIZE, WANT_TPI, true>(b, tpi_out, std_out)));
+        } else if constexpr (std_ring_both_fits(SIZE)) {  // (up to 41 px)
+            TOPO_TRY((launch_std_ring<SIZE, WANT_TPI, kStdBoth>(b, tpi_out, std_out)));
+        }
+        constexpr int second = std_spec_both_fits(SIZE) ? kDiscFracSpecBoth : std_ring_both_fits(SIZE) ? kDiscFracStdRingBoth : 0;
+        return deferred(RTH, 0, route(std_ring_spec(SIZE) ? kDiscFirstSpec4 : kDiscFirstStdRing, RTH, second | kDiscDeferred));
+    } else if constexpr (std_takes_march_pair(SIZE)) {
+        // sum x (and TPI) marching, then sum u^2 -> STD marching over the same runs, then the general kernel
+        TOPO_TRY((launch_march<SIZE, TH12, 12, WANT_TPI, true>(b, tpi_out)));
+        TOPO_TRY((launch_std_march<SIZE, TH12, 12>(b, std_out)));
+        return deferred(TH12, 0, route(kDiscFirstMarch, TH12, kDiscStdMarch | kDiscDeferred));
+    } else {
+        // one general kernel (two passes per tile, the second one out of L2) moves three planes where the marching pair moves
+        // five; on small discs the chains are too short to matter, on the largest the marching tiles are too low
+        return note_disc_if_ok(launch_wave<SIZE, TH8, 8, WANT_TPI, true>(b, tpi_out, std_out), route(kDiscFirstGeneral, TH8, 0));
+    }
+}
+
+template <int SIZE>
+int launch_wave_any(const Block& b, float* tpi_out, float* std_out) {
+    if (std_out == nullptr) return launch_tpi_any<SIZE>(b, tpi_out);
+    if (tpi_out == nullptr) return launch_std_any<SIZE, false>(b, nullptr, std_out);
+    return launch_std_any<SIZE, true>(b, tpi_out, std_out);
 }
 
 }  // namespace
