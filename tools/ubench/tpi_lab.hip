@@ -9,6 +9,8 @@
 //     variant ring  : tpi_ring_kernel<67, 8> (round 2, 8 columns per lane)
 //     variants any_tpi / any_std / any_tpi_std : the product's dispatch for 67 px, compiled with this build's flags
 //   (-DMARCH_DYN_ROWS=0/1, -DCHAIN_PRIO=0/1, -DMARCH_STAMPS)
+//   -DWIDE_STAMPS=1/2 (variant any_tpi): clock stamps of tpi_ring_wide_kernel<67> at the end of a phase, printed per wave for
+//   two blocks - 1 with the chain waves' output stores drained in front of the barrier, 2 without (the kernel as built)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -103,6 +105,23 @@ int main(int argc, char** argv) {
         best = ms < best ? ms : best;
         sum += ms;
     }
+#if WIDE_STAMPS
+    {
+        // what the last launch of tpi_ring_wide_kernel left (variant any_tpi at 67 px): per stamped block and wave the ticks
+        // of its phases, of the chain waves' store drain in front of the phase barrier, of the barrier, of a stamp pair
+        unsigned long long st[topo::kWideStampBlocks][topo::kWideStampWaves][topo::kWideStampFields];
+        if (hipMemcpyFromSymbol(st, HIP_SYMBOL(topo::wide_stamps), sizeof(st)) != hipSuccess) return 1;
+        for (int k = 0; k < topo::kWideStampBlocks; ++k)
+            for (int w = 0; w < topo::kWideStampWaves; ++w) {
+                const unsigned long long* s = st[k][w];
+                const double n = s[0] ? (double)s[0] : 1.0;
+                printf("blk %s wave %2d (%s): phases %llu  ticks a phase %.1f | drain %.1f | barrier %.1f | stamp pair %.1f"
+                       "   drain less the pair: %.2f %% of a phase\n",
+                       k ? "mid" : "  0", w, w < 3 ? "stager" : "chain ", s[0], s[1] / n, s[2] / n, s[3] / n, s[4] / n,
+                       s[1] ? 100.0 * ((double)s[2] - (double)s[4]) / (double)s[1] : 0.0);
+            }
+    }
+#endif
     unsigned long long* d_bad = nullptr;
     unsigned long long bad[2] = {0, 0};
     CK(topo_amd_malloc((void**)&d_bad, 16));

@@ -13,7 +13,7 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r09_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r10_tpi67_wide_valu_count.json
 
 wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
@@ -128,6 +128,10 @@ def wide():
     mn = [x.split()[0] for x in ph]
     assert mn.count("ds_read_b64") == 3 * 55, "a row pair: 55 prefix rows of three reads"
     assert mn.count("s_setprio") in (0, 4), "no priority ladder, or the sweep's 3, 2, 1, 0 (WIDE_PRIO)"
+    # a chain wave has no load in flight, only its output stores: a vmcnt wait in its phase loop can only wait for those
+    # (round 10: the staging waves' last loads, open where the two paths meet, put four such waits there)
+    vm_waits = [i for i, x in enumerate(ph) if x.startswith("s_waitcnt") and "vmcnt" in x]
+    assert not vm_waits, f"the chain waves' phase loop waits for its output stores at instructions {vm_waits}"
     row = ph
     o = mn
     n_addr = address_adds(row)
@@ -137,7 +141,8 @@ def wide():
     kinds["plain"] -= n_addr  # (plain adds: priced as before)
     kinds["ds_read_address"] = n_addr
     pair = {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b64": o.count("ds_read_b64"), "s_nop": o.count("s_nop"),
-            "salu": sum(1 for x in o if x.startswith("s_")), "ns": round(ns, 1)}
+            "salu": sum(1 for x in o if x.startswith("s_")), "global_store_dwordx2": o.count("global_store_dwordx2"),
+            "vmcnt_waits": len(vm_waits), "instructions": len(o), "ns": round(ns, 1)}
     # per output row: half the pair
     valu = valu[:len(valu) // 2]
     kinds = Counter({k: v / 2 for k, v in kinds.items()})

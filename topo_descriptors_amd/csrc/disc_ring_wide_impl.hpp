@@ -232,6 +232,24 @@ struct WSweep {
 #define WIDE_PRIO 0
 #endif
 
+// (lab switch: 1 stamps the clock around what a wave waits for at the end of a phase - a drain of the chain waves' output
+// stores (s_waitcnt vmcnt(0), which the compiler put there itself until round 10), then the barrier - summed per wave in
+// scalar registers and written by two blocks with ordinary stores when the kernel ends; 2 stamps the same points and
+// drains nothing, the kernel as it is built.  tools/ubench/tpi_lab.hip -DWIDE_STAMPS=1, profiles/r10_tpi67_store_drain.txt)
+#ifndef WIDE_STAMPS
+#define WIDE_STAMPS 0
+#endif
+#if WIDE_STAMPS
+constexpr int kWideStampBlocks = 2, kWideStampWaves = 11, kWideStampFields = 5;
+// per stamped block and wave: phases, ticks in all of them, in the drain, at the barrier, in a back-to-back stamp pair
+__device__ unsigned long long wide_stamps[kWideStampBlocks][kWideStampWaves][kWideStampFields];
+__device__ __forceinline__ uint32_t wide_now() {  // (the low word: a phase is a few thousand ticks, a launch's sums fit)
+    const uint32_t t = (uint32_t)__builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the stamp is taken here, not where its first use falls
+    return t;
+}
+#endif
+
 typedef uint32_t u32x2w __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const char lds_char;
 typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
@@ -398,6 +416,9 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
     const bool stager = wave < SW;
     const int scol = 128 * wave + 2 * lane;  // a staging lane's first staged column (and the next one)
     int seen_tiles = 0, seen_frac = 0;
+#if WIDE_STAMPS
+    uint32_t ts_n = 0, ts_all = 0, ts_drain = 0, ts_bar = 0, ts_pair = 0, ts_prev = 0;
+#endif
 
 #pragma unroll 1
     for (int pos = first; pos < last;) {
@@ -558,14 +579,49 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                 }
             }
             advance_wslot();
+#if WIDE_STAMPS
+            const uint32_t t0 = wide_now();
+            if constexpr (!stg && WIDE_STAMPS == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t1 = wide_now();
+#endif
             __syncthreads();
+#if WIDE_STAMPS
+            const uint32_t t2 = wide_now(), t3 = wide_now();
+            if (ph > 0) {  // (a run's first phase has no phase before it to measure from)
+                ts_n += 1;
+                ts_all += t2 - ts_prev;
+                ts_drain += t1 - t0;
+                ts_bar += t2 - t1;
+                ts_pair += t3 - t2;
+            }
+            ts_prev = t2;
+#endif
             fold((ph + 1) & 1);
+        }
+        if constexpr (stg) {
+            // The last phase's loads (the batch behind the run, clamped rows, never staged) are taken up HERE, so that no
+            // load is in flight where this path meets the chain waves' at the top of the run loop.  The compiler's wait
+            // counts are per program point, not per wave: with these sixteen loads open at that point it guards every
+            // write of one of their registers (v10 .. v41, which the sweep reuses) in the CHAIN waves' phase loop as well -
+            // s_waitcnt vmcnt(0) in front of the phase barrier and vmcnt(12), (7), (0) at the sweep's start.  A chain wave
+            // has no load in flight, only its six output stores of the phase, and so waited out their round trip in
+            // every phase with nothing to overlap it.  One wait per run of the staging waves instead.
+#pragma unroll
+            for (int r = 0; r < B; ++r) asm volatile("" ::"v"(va[r].x), "v"(va[r].y));
         }
         };
         if (stager) run_phases(std::true_type{});
         else run_phases(std::false_type{});
         pos += run_tiles;
     }
+#if WIDE_STAMPS
+    static_assert(WideCfg<SIZE>::NW == kWideStampWaves, "one record per wave");
+    if (lane == 0 && (vb == 0 || vb == nb / 2)) {
+        unsigned long long* o = wide_stamps[vb == 0 ? 0 : 1][wave];
+        o[0] = (unsigned long long)ts_n, o[1] = (unsigned long long)ts_all, o[2] = (unsigned long long)ts_drain;
+        o[3] = (unsigned long long)ts_bar, o[4] = (unsigned long long)ts_pair;
+    }
+#endif
     if (p.report != nullptr && vb == nb / 2 && threadIdx.x == 0) {
         __hip_atomic_store(p.report + 1, (uint32_t)seen_frac, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(p.report, (uint32_t)seen_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
