@@ -366,7 +366,8 @@ int topo_amd_valley_ridge_std_dev(const float* in, int ny, int nx, const float* 
                                   float* dir_out, float moments_out[2]);
 /* What the calling thread's last valley / ridge call did about the moments (for tests and diagnostics): 0 taken from the
  * caller (topo_amd_valley_ridge_dev / _f32 / _raw), 1 formed on the device in numpy's order (topo_amd_valley_ridge_std_dev
- * / _std_raw / _packed), 2 the float64 all-reduce of a sharded call.  topo_amd_valley_route is not touched by this.      */
+ * / _std_raw / _packed), 2 the float64 all-reduce of a sharded call, 3 numpy's order across the shards
+ * (topo_amd_shard_valley_ridge_std).  topo_amd_valley_route is not touched by this.                                      */
 int topo_amd_valley_moments_route(int* route);
 
 /* Gaps of a DEM filled with the nearest valid sample along x: replaces hlp.fill_na(dem_ds) (reference helpers.py:137-154,
@@ -643,7 +644,11 @@ int topo_amd_shard_sx_multi(float* block, int rows_local, int row0, int gny, int
  * topo_amd_halo_rows(VALLEY_RIDGE, largest kernel side).  The mean and standard deviation of
  * the whole DEM come from float64 moments of the owned rows and one ncclAllReduce (the only
  * true collective on the path; exact, hence the same for every sharding, on a DEM of whole
- * metres).                                                                                  */
+ * metres).  That is route 2 of topo_amd_valley_moments_route, and so is _smoothed below.
+ * Route 3, topo_amd_shard_valley_ridge_std: the moments are numpy's own float32 mean() /
+ * std() of the WHOLE raster (topo_amd_shard_mean_std_f32), bit for bit and for every sharding
+ * and every DEM - so a sharded index is the single GPU's topo_amd_valley_ridge_std_dev on the
+ * owned rows, near-tied directions included.                                                */
 int topo_amd_shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx,
                                 const float* taps, const int32_t* ksize, const float* angles,
                                 int n_angles, int n_planes, float* norm_out, float* dir_out);
@@ -680,6 +685,28 @@ int topo_amd_shard_tpi_std_smoothed(float* block, int rows_local, int row0, int 
 int topo_amd_shard_valley_ridge_smoothed(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
                                          const int32_t* ksize, const float* angles, int n_angles, int n_planes,
                                          double sigma, float* norm_out, float* dir_out, double* moments_out);
+/* Collective: topo_amd_mean_std_f32_dev of the WHOLE raster [gny x nx] from row shards, bit for bit, on every rank.  owned: the
+ * first row this rank owns (device pointer), rows_local of them from global row row0; the ranks' rows must tile the raster
+ * (refused otherwise, after the collective, on every rank alike).  numpy's chunks sit at global sample offsets k * chunk: a
+ * rank sums the chunks that lie wholly inside its samples on its GPU (the kernel of topo_amd_mean_std_f32_dev, started at its
+ * first global chunk boundary) and contributes the samples before / after its first / last boundary as they are.  Per pass
+ * (sum; squared deviations) the parts travel in ONE ncclAllReduce over an array whose size follows from (gny, nx, chunk,
+ * communicator size) alone - chunk sums indexed by global chunk, then per rank a header and two fragment areas of chunk
+ * samples (first pass only) - each word written by one rank and zero elsewhere, summed as unsigned integers: every rank gets
+ * every word bit for bit, and runs the same chain over them on its host.  chunk: as topo_amd_mean_std_f32_dev
+ * (TOPO_AMD_EINVAL otherwise).  Refused when the shard is part of a raster and no communicator exists.  Loop-back mode: the
+ * rank's rows stand at every placement of the periodic stack (gny / rows_local copies; gny % rows_local != 0 is
+ * TOPO_AMD_EINVAL), so the call yields the moments of the stacked raster.                                                 */
+int topo_amd_shard_mean_std_f32(const float* owned, int rows_local, int row0, int gny, int nx, size_t chunk, float* mean,
+                                float* stdev);
+/* topo_amd_shard_valley_ridge_smoothed standardised with those moments (route 3): with sigma <= 0 of the owned raw rows,
+ * otherwise of the owned SMOOTHED rows in the workspace plane; exchange, ghost depths, layout declaration and kernels are
+ * those of the two calls above.  moments_out (host float[2], or NULL): the (mean, std) the call standardised with.  Given the
+ * same moments the kernels give the single block's bits on every row block, so this is topo_amd_valley_ridge_std_dev of the
+ * whole (smoothed) raster on the owned rows, bit for bit, for every sharding.                                              */
+int topo_amd_shard_valley_ridge_std(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
+                                    const int32_t* ksize, const float* angles, int n_angles, int n_planes, double sigma,
+                                    size_t chunk, float* norm_out, float* dir_out, float moments_out[2]);
 /* topo_amd_fill_na_dev on the owned rows: row-local, no exchange, no RCCL call.  out may be the owned rows themselves (in
  * place); missing (uint8 rows_local x nx) may be NULL; x_coords: the WHOLE DEM's, one per column.  An in-place fill drops
  * the raster class declared for the rows it writes, and the next shard call re-classifies - collectively.  So this call is

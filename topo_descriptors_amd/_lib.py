@@ -176,6 +176,9 @@ SIGNATURES = {
                                                   _vp]),
     "topo_amd_shard_valley_ridge_smoothed": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp,
                                                        C.c_int, C.c_int, C.c_double, _vp, _vp, _f64p]),
+    "topo_amd_shard_mean_std_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, _f32p, _f32p]),
+    "topo_amd_shard_valley_ridge_std": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i32p, _vp, C.c_int, C.c_int,
+                                                  C.c_double, C.c_size_t, _vp, _vp, _f32p]),
     "topo_amd_shard_fill_na": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_double, _vp, _vp]),
 }
 

@@ -268,6 +268,16 @@ int launch_mean_std(const float* in, size_t count, double* mean, double* stdev);
 int launch_moments(const float* in, size_t count, double pivot, bool pivot_is_first_sample, double* sum, double* sumsq);
 // numpy's own float32 mean() / std() of count device floats, bit for bit (moments_np.hip); chunk: numpy's buffer size in samples
 int launch_mean_std_np(const float* in, size_t count, size_t chunk, float* mean, float* stdev);
+// the same on row shards (moments_np.hip: the layout of the words a pass exchanges is stated there).  np_shard_words: the size of
+// a pass's array for `slots` ranks, from (count, chunk, slots) alone; launch_np_shard_parts: queues one rank's parts into the
+// zeroed device array; np_shard_sum: the host chain over the reduced array, the same floats in the same order on every rank.
+bool np_chunk_ok(size_t chunk);
+size_t np_shard_partials(size_t count, size_t chunk);
+size_t np_shard_words(size_t count, size_t chunk, int slots, bool fragments);
+int launch_np_shard_parts(const float* owned, size_t first, size_t n, size_t count, size_t chunk, int slot, bool sq, float mean,
+                          uint32_t* d_words);
+int np_shard_sum(const uint32_t* words, const uint32_t* fragments, size_t count, size_t chunk, int slots, bool sq, float mean,
+                 float* sum);
 int launch_valley_ridge(const Block& b, const float* taps, const int32_t* ksize, const float* angles, int n_angles,
                         int n_planes, double mean, double stdev, float* norm_out, float* dir_out);
 

@@ -15,7 +15,10 @@
 // downloads them (131072 floats for 32768^2), finishes longer chunks' trees, runs the sequential chain and reduces the tail
 // of fewer than `chunk` samples itself.  Every float32 operation below is a single IEEE operation: this file is built with
 // -ffp-contract=off and without fast-math, and the device code spells the roundings out (__fadd_rn ...).
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "common.hpp"
@@ -176,6 +179,175 @@ int launch_mean_std_np(const float* in, size_t count, size_t chunk, float* mean,
     TOPO_TRY(np_sum(in, count, chunk, true, m, tail, &sum2));
     *mean = m;
     *stdev = std::sqrt(sum2 / n);
+    return TOPO_AMD_OK;
+}
+
+// ---- the same order on row shards (topo_amd_shard_mean_std_f32) ----------------------------------------------------------------
+// A rank owns samples [first, first + n) of the raster's `count`; numpy's chunks sit at GLOBAL offsets k * chunk.  What the
+// ranks exchange in a pass is an array of 32-bit WORDS whose size follows from (count, chunk, slots) alone:
+//   words [0, np_shard_partials): the partial sums of the full chunks, indexed by global chunk (chunk / 8192 partials for a
+//     chunk longer than a tile) - a rank fills the chunks that lie wholly inside its samples with np_partials_kernel started
+//     at its first global chunk boundary;
+//   pass 1 only, per slot (rank): 4 header words {first, n} as two 64-bit numbers, then the head and the tail fragment (the
+//     samples before the first / after the last chunk boundary; all of them as head when there is no boundary), each in an
+//     area of min(chunk, count) words.
+// Every word is written by one rank and zero on all others, so a sum-reduction of the array as unsigned integers hands every
+// rank every word bit for bit (NaN payloads and -0.0f included); np_shard_sum then runs numpy's chain over the same words
+// on every rank: the chunk trees' upper levels, the straddling chunks put together from the fragments and summed with
+// pairwise_host, the sums added one after the other from 0.0f.
+namespace {
+constexpr size_t kNpSlotHeader = 4;
+
+struct NpWindow {
+    size_t c0, c1;            // global chunks [c0, c1) lie wholly inside (c0 > c1: no chunk boundary among the samples)
+    size_t head, tail, tail_at;  // fragment lengths, the tail's global offset
+};
+NpWindow np_window(size_t first, size_t n, size_t chunk) {
+    NpWindow w;
+    const size_t end = first + n;
+    w.c0 = (first + chunk - 1) / chunk;
+    w.c1 = end / chunk;
+    if (w.c0 > w.c1) {
+        w.head = n, w.tail = 0, w.tail_at = end;
+    } else {
+        w.head = w.c0 * chunk - first, w.tail = end - w.c1 * chunk, w.tail_at = w.c1 * chunk;
+    }
+    return w;
+}
+size_t np_frag_cap(size_t count, size_t chunk) { return chunk < count ? chunk : count; }
+size_t np_per(size_t chunk) { return chunk < (size_t)kTile ? chunk : (size_t)kTile; }
+
+// header and fragments of one slot: words[0 .. 4) the header, [4, 4 + cap) the head, [4 + cap, 4 + 2 cap) the tail
+__global__ __launch_bounds__(kNpThreads) void np_fragments_kernel(const uint32_t* __restrict__ owned, unsigned long long first,
+                                                                  unsigned long long n, unsigned long long head,
+                                                                  unsigned long long tail, unsigned long long cap,
+                                                                  uint32_t* __restrict__ words) {
+    const size_t i = (size_t)blockIdx.x * kNpThreads + threadIdx.x;
+    if (i == 0) {
+        words[0] = (uint32_t)first, words[1] = (uint32_t)(first >> 32);
+        words[2] = (uint32_t)n, words[3] = (uint32_t)(n >> 32);
+    }
+    if (i < head && i < cap) words[kNpSlotHeader + i] = owned[i];
+    if (i < tail && i < cap) words[kNpSlotHeader + cap + i] = owned[n - tail + i];
+}
+float word_float(uint32_t w) {
+    float f;
+    std::memcpy(&f, &w, sizeof(f));
+    return f;
+}
+}  // namespace
+
+bool np_chunk_ok(size_t chunk) { return chunk >= (size_t)kLeaf && (chunk & (chunk - 1)) == 0; }
+
+size_t np_shard_partials(size_t count, size_t chunk) { return (count / chunk) * (chunk / np_per(chunk)); }
+
+size_t np_shard_words(size_t count, size_t chunk, int slots, bool fragments) {
+    return np_shard_partials(count, chunk) + (fragments ? (size_t)slots * (kNpSlotHeader + 2 * np_frag_cap(count, chunk)) : 0);
+}
+
+// The window form of np_sum's device half: queues, on the compute stream, the partial sums of the full global chunks inside
+// owned[0, n) = samples [first, first + n) of `count` into d_words (zeroed by the caller) and, !sq, the slot's header and
+// fragments.  sq: of the squared deviations from `mean`.
+int launch_np_shard_parts(const float* owned, size_t first, size_t n, size_t count, size_t chunk, int slot, bool sq, float mean,
+                          uint32_t* d_words) {
+    Context& c = ctx();
+    TOPO_REQUIRE(n >= 1 && first + n <= count, "shard_mean_std_f32: samples [%zu, %zu) of a raster of %zu", first, first + n, count);
+    const NpWindow w = np_window(first, n, chunk);
+    if (w.c1 > w.c0) {
+        const size_t per = np_per(chunk), covered = (w.c1 - w.c0) * chunk, n_partials = covered / per;
+        const size_t tiles = (covered + kTile - 1) / kTile;
+        TOPO_REQUIRE(tiles <= 0x7fffffffu, "shard_mean_std_f32: %zu samples are more than one launch covers", n);
+        const float* in = owned + (w.c0 * chunk - first);  // the first global chunk boundary: 16-byte aligned whenever nx % 4 == 0
+        float* partial = reinterpret_cast<float*>(d_words) + w.c0 * (chunk / per);
+        const bool vec = ((uintptr_t)in & 15) == 0;
+        const dim3 grid((unsigned)tiles), block(kNpThreads);
+        const int group = (int)(per / kLeaf);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, c.compute, in, covered, mean, group, n_partials, partial);
+        };
+        if (vec) {
+            sq ? launch(np_partials_kernel<true, true>) : launch(np_partials_kernel<true, false>);
+        } else {
+            sq ? launch(np_partials_kernel<false, true>) : launch(np_partials_kernel<false, false>);
+        }
+        TOPO_HIP(hipGetLastError());
+    }
+    if (!sq) {
+        const size_t cap = np_frag_cap(count, chunk);
+        TOPO_REQUIRE(w.head <= cap && w.tail <= cap, "shard_mean_std_f32: fragments of %zu / %zu samples", w.head, w.tail);
+        uint32_t* area = d_words + np_shard_partials(count, chunk) + (size_t)slot * (kNpSlotHeader + 2 * cap);
+        const size_t most = std::max<size_t>(1, std::max(w.head, w.tail));
+        hipLaunchKernelGGL(np_fragments_kernel, dim3((unsigned)((most + kNpThreads - 1) / kNpThreads)), dim3(kNpThreads), 0, c.compute,
+                           reinterpret_cast<const uint32_t*>(owned), (unsigned long long)first, (unsigned long long)n,
+                           (unsigned long long)w.head, (unsigned long long)w.tail, (unsigned long long)cap, area);
+        TOPO_HIP(hipGetLastError());
+    }
+    return TOPO_AMD_OK;
+}
+
+// The host chain of a pass.  `words`: the pass's reduced array (its partial sums); `fragments`: pass 1's reduced array (headers
+// and raw fragments; == words in pass 1).  Refuses slots that do not tile the raster's samples.
+int np_shard_sum(const uint32_t* words, const uint32_t* fragments, size_t count, size_t chunk, int slots, bool sq, float mean,
+                 float* sum) {
+    const size_t n_chunks = count / chunk, ppc = chunk / np_per(chunk), cap = np_frag_cap(count, chunk);
+    struct Slot {
+        size_t first, n;
+        const uint32_t* head;
+        NpWindow w;
+    };
+    std::vector<Slot> s;
+    for (int k = 0; k < slots; ++k) {
+        const uint32_t* a = fragments + np_shard_partials(count, chunk) + (size_t)k * (kNpSlotHeader + 2 * cap);
+        Slot t{(size_t)a[0] | (size_t)a[1] << 32, (size_t)a[2] | (size_t)a[3] << 32, a + kNpSlotHeader, {}};
+        if (t.n == 0) continue;
+        TOPO_REQUIRE(t.first <= count && t.n <= count - t.first, "shard_mean_std_f32: a rank reports samples [%zu, +%zu) of %zu",
+                     t.first, t.n, count);
+        t.w = np_window(t.first, t.n, chunk);
+        s.push_back(t);
+    }
+    std::sort(s.begin(), s.end(), [](const Slot& a, const Slot& b) { return a.first < b.first; });
+    size_t at = 0;
+    for (const Slot& t : s) {
+        TOPO_REQUIRE(t.first == at, "shard_mean_std_f32: the ranks' rows do not tile the raster (sample %zu is owned %s)", at,
+                     t.first > at ? "by nobody" : "twice");
+        at = t.first + t.n;
+    }
+    TOPO_REQUIRE(at == count, "shard_mean_std_f32: the ranks' rows do not tile the raster (%zu of %zu samples)", at, count);
+    std::vector<char> full(n_chunks, 0);  // summed on some rank's GPU
+    for (const Slot& t : s)
+        for (size_t k = t.w.c0; k < t.w.c1; ++k) full[k] = 1;
+    std::vector<float> tree(ppc), piece;
+    float acc = 0.0f;
+    const size_t total = n_chunks + (count % chunk ? 1 : 0);
+    for (size_t k = 0; k < total; ++k) {
+        if (k < n_chunks && full[k]) {
+            for (size_t i = 0; i < ppc; ++i) tree[i] = word_float(words[k * ppc + i]);
+            for (size_t m = ppc; m > 1; m /= 2)
+                for (size_t i = 0; i < m / 2; ++i) tree[i] = tree[2 * i] + tree[2 * i + 1];
+            acc = acc + tree[0];
+            continue;
+        }
+        const size_t lo = k * chunk, hi = std::min(lo + chunk, count);
+        piece.clear();
+        for (const Slot& t : s) {
+            if (t.first + t.n <= lo || t.first >= hi) continue;
+            auto take = [&](const uint32_t* from, size_t start, size_t len) {
+                if (len == 0 || start < lo || start >= hi) return;
+                for (size_t i = 0; i < len; ++i) piece.push_back(word_float(from[i]));
+            };
+            take(t.head, t.first, t.w.head);
+            take(t.head + cap, t.w.tail_at, t.w.tail);
+        }
+        TOPO_REQUIRE(piece.size() == hi - lo, "shard_mean_std_f32: %zu of the %zu samples of chunk %zu arrived", piece.size(), hi - lo, k);
+        if (sq) {
+            for (float& v : piece) {
+                const float d = v - mean;
+                v = d * d;
+            }
+        }
+        acc = acc + pairwise_host(piece.data(), piece.size());
+    }
+    *sum = acc;
     return TOPO_AMD_OK;
 }
 

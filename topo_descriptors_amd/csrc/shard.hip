@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "capi.hpp"
 
@@ -585,17 +586,87 @@ int shard_moments(const float* owned, int rows_local, int nx, double* mean, doub
     return TOPO_AMD_OK;
 }
 
+// One pass of the numpy-order moments across the shards (moments_np.hip): the array of `words` the ranks' parts were queued
+// into on the compute stream is sum-reduced as unsigned integers on the communication stream - every word is one rank's, zero
+// on the others, so every rank receives every word bit for bit - and downloaded behind it.  A communicator of one rank (loop-
+// back: the rank filled every slot itself) has nothing to reduce.
+int np_exchange(uint32_t* d_words, size_t words, std::vector<uint32_t>* host) {
+    Context& c = ctx();
+    host->resize(words);
+    hipStream_t from = c.compute;
+    if (g_comm.size > 1) {
+        TOPO_REQUIRE(g_comm.comm != nullptr, "shard_mean_std_f32: call topo_amd_comm_init first");
+        TOPO_HIP(hipEventRecord(c.input_ready, c.compute));
+        TOPO_HIP(hipStreamWaitEvent(c.comm, c.input_ready, 0));
+        TOPO_NCCL(ncclAllReduce(d_words, d_words, words, ncclUint32, ncclSum, g_comm.comm, c.comm));
+        from = c.comm;
+    }
+    TOPO_HIP(hipMemcpyAsync(host->data(), d_words, words * sizeof(uint32_t), hipMemcpyDeviceToHost, from));
+    TOPO_HIP(hipStreamSynchronize(from));
+    return TOPO_AMD_OK;
+}
+
+// numpy's own float32 mean() / std() of the WHOLE raster from the rows this rank owns (route 3): per pass the rank's part of
+// numpy's summation tree on its GPU, one collective, one download, and the same host chain over the same floats on every
+// rank - the bits topo_amd_mean_std_f32_dev gives on the whole raster, however the rows are cut.  Loop-back: the rank stands
+// for every placement of the periodic stack of its rows and fills every placement's slot.
+int shard_mean_std_np(const float* owned, int rows_local, int row0, int gny, int nx, size_t chunk, float* mean, float* stdev) {
+    TOPO_REQUIRE(owned && rows_local >= 1 && row0 >= 0 && row0 + rows_local <= gny && nx >= 1, "shard_mean_std_f32: bad arguments");
+    TOPO_REQUIRE(np_chunk_ok(chunk), "shard_mean_std_f32: chunk %zu (a power of two, 128 at least)", chunk);
+    TOPO_REQUIRE(rows_local == gny || g_comm.size > 1 || halo_loopback(),
+                 "shard_mean_std_f32: rows [%d, %d) of a raster of %d rows, but no communicator exists (topo_amd_comm_init) - the other "
+                 "shards' samples cannot be added", row0, row0 + rows_local, gny);
+    const bool stacked = halo_loopback() && rows_local < gny;
+    TOPO_REQUIRE(!stacked || (gny % rows_local == 0 && row0 % rows_local == 0),
+                 "shard_mean_std_f32: loop-back stacks whole copies of the rank's rows, %d rows at row %d do not tile %d", rows_local, row0, gny);
+    const int slots = stacked ? gny / rows_local : g_comm.size;
+    const size_t count = (size_t)gny * nx, n = (size_t)rows_local * nx;
+    const size_t words1 = np_shard_words(count, chunk, slots, true), words2 = np_shard_words(count, chunk, slots, false);
+    void* d = nullptr;
+    TOPO_TRY(workspace(0, words1 * sizeof(uint32_t), &d));
+    uint32_t* d_words = (uint32_t*)d;
+    Context& c = ctx();
+    std::vector<uint32_t> first_pass, second_pass;
+    auto pass = [&](bool sq, float m, size_t words, std::vector<uint32_t>* host) {
+        TOPO_HIP(hipMemsetAsync(d_words, 0, words * sizeof(uint32_t), c.compute));
+        for (int k = 0; k < (stacked ? slots : 1); ++k) {
+            const int slot = stacked ? k : g_comm.rank;
+            const size_t first = (size_t)(stacked ? k * rows_local : row0) * nx;
+            TOPO_TRY(launch_np_shard_parts(owned, first, n, count, chunk, slot, sq, m, d_words));
+        }
+        return np_exchange(d_words, words, host);
+    };
+    float sum = 0.0f, sum2 = 0.0f;
+    TOPO_TRY(pass(false, 0.0f, words1, &first_pass));
+    TOPO_TRY(np_shard_sum(first_pass.data(), first_pass.data(), count, chunk, slots, false, 0.0f, &sum));
+    const float m = sum / (float)count;
+    if (words2) TOPO_TRY(pass(true, m, words2, &second_pass));  // (no whole chunk in the raster: the fragments are all there is)
+    TOPO_TRY(np_shard_sum(second_pass.data(), first_pass.data(), count, chunk, slots, true, m, &sum2));
+    *mean = m;
+    *stdev = std::sqrt(sum2 / (float)count);
+    return TOPO_AMD_OK;
+}
+
 int shard_valley_ridge(float* block, int rows_local, int row0, int gny, int nx, const float* taps, const int32_t* ksize,
-                       const float* angles, int n_angles, int n_planes, float* norm_out, float* dir_out, double* moments_out) {
+                       const float* angles, int n_angles, int n_planes, float* norm_out, float* dir_out, double* moments_out,
+                       size_t np_chunk = 0, float* np_moments_out = nullptr) {
     TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1,
                  "shard_valley_ridge: NULL argument");
-    note_valley_moments(2);  // (the shards' float64 all-reduce)
     int above = 0, below = 0;
     (void)valley_ridge_reach(ksize, n_angles, &above, &below);
     Shard s;
     TOPO_TRY(open_shard(&block, rows_local, row0, gny, nx, above, below, "shard_valley_ridge", &s));
     double mean = 0.0, stdev = 0.0;
-    TOPO_TRY(shard_moments(s.owned.in, rows_local, nx, &mean, &stdev, moments_out));
+    if (np_chunk) {  // numpy's float32 moments of the whole raster (route 3)
+        float m = 0.0f, sd = 0.0f;
+        TOPO_TRY(shard_mean_std_np(s.owned.in, rows_local, row0, gny, nx, np_chunk, &m, &sd));
+        mean = (double)m, stdev = (double)sd;
+        if (np_moments_out) np_moments_out[0] = m, np_moments_out[1] = sd;
+        note_valley_moments(3);
+    } else {
+        note_valley_moments(2);  // (the shards' float64 all-reduce)
+        TOPO_TRY(shard_moments(s.owned.in, rows_local, nx, &mean, &stdev, moments_out));
+    }
     return run_three(block, s, above, below, [&](const Block& view, int o0, int on) {
         Block b;
         TOPO_TRY(out_block(view, o0, on, above, below, "shard_valley_ridge", &b));
@@ -843,6 +914,43 @@ int topo_amd_shard_valley_ridge_smoothed(float* block, int rows_local, int row0,
     forget_plane(norm_out, rows_local, nx);
     forget_plane(dir_out, rows_local, nx);
     return launch_valley_ridge(d, taps, ksize, angles, n_angles, n_planes, mean, stdev, norm_out, dir_out);
+}
+
+// numpy's own float32 mean() / std() of the whole sharded raster: see include/topo_amd.h
+int topo_amd_shard_mean_std_f32(const float* owned, int rows_local, int row0, int gny, int nx, size_t chunk, float* mean,
+                                float* stdev) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(mean && stdev, "shard_mean_std_f32: NULL output");
+    return shard_mean_std_np(owned, rows_local, row0, gny, nx, chunk, mean, stdev);
+}
+
+int topo_amd_shard_valley_ridge_std(float* block, int rows_local, int row0, int gny, int nx, const float* taps,
+                                    const int32_t* ksize, const float* angles, int n_angles, int n_planes, double sigma,
+                                    size_t chunk, float* norm_out, float* dir_out, float moments_out[2]) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(np_chunk_ok(chunk), "shard_valley_ridge_std: chunk %zu (a power of two, 128 at least)", chunk);
+    if (!(sigma > 0.0))
+        return shard_valley_ridge(block, rows_local, row0, gny, nx, taps, ksize, angles, n_angles, n_planes, norm_out, dir_out,
+                                  nullptr, chunk, moments_out);
+    TOPO_REQUIRE(block && taps && ksize && angles && norm_out && dir_out && n_angles >= 1, "shard_valley_ridge_std: NULL argument");
+    int up = 0, down = 0;
+    (void)valley_ridge_reach(ksize, n_angles, &up, &down);
+    Shard s;
+    SmoothedPlane sp;
+    TOPO_TRY(smoothed_shard(&block, rows_local, row0, gny, nx, up, down, sigma, "shard_valley_ridge_std", &s, &sp));
+    // the standardisation of the smoothed field (topo.py:424-427) with numpy's float32 moments of the whole smoothed raster:
+    // the parts of the OWNED smoothed rows of every rank, where _smoothed takes its float64 moments
+    float mean = 0.0f, stdev = 0.0f;
+    TOPO_TRY(shard_mean_std_np(sp.row(row0), rows_local, row0, gny, nx, chunk, &mean, &stdev));
+    note_valley_moments(3);
+    if (moments_out) moments_out[0] = mean, moments_out[1] = stdev;
+    const Block d = sp.block(row0, rows_local, gny);
+    TOPO_TRY(check_block(d, up, down, "shard_valley_ridge_std"));
+    forget_plane(norm_out, rows_local, nx);
+    forget_plane(dir_out, rows_local, nx);
+    return launch_valley_ridge(d, taps, ksize, angles, n_angles, n_planes, (double)mean, (double)stdev, norm_out, dir_out);
 }
 
 int topo_amd_shard_fill_na(float* block, int rows_local, int row0, int gny, int nx, const double* x_coords,

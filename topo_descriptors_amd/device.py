@@ -207,7 +207,8 @@ def valley_route():
 
 def valley_moments_route():
     """What the calling thread's last valley / ridge call did about the DEM's mean and std: 0 taken from the caller, 1 formed
-    on the device in numpy's order (``mean_std_numpy``), 2 the float64 all-reduce of a sharded call."""
+    on the device in numpy's order (``mean_std_numpy``), 2 the float64 all-reduce of a sharded call, 3 numpy's order across the
+    shards (``ShardedDEM.valley_ridge(numpy_moments=True)``)."""
     n = C.c_int32()
     _lib.check(_lib.lib().topo_amd_valley_moments_route(C.byref(n)), "valley_moments_route")
     return n.value

@@ -379,6 +379,87 @@ def numpy_order_moments(array, chunk=None):
         return mean, np.sqrt(numpy_order_sum(dev * dev, chunk) / n)
 
 
+# ---- the same order on row shards --------------------------------------------------------------------------------------------
+# A rank owns samples [first_sample, first_sample + n) of the raster's `count`.  numpy's chunks sit at GLOBAL offsets k * chunk,
+# so the rank's part of the summation tree is: one sum per global chunk that lies wholly inside its samples, and the samples
+# before its first / after its last chunk boundary as they are (head / tail, each fewer than `chunk`).  A chunk that straddles
+# ranks - and the raster's partial last chunk - is put together from those fragments and summed pairwise by whoever combines
+# the parts; the chain over the chunk sums then runs over the same floats on every rank (``ShardedDEM.mean_std_numpy``,
+# ``topo_amd_shard_mean_std_f32``).
+def numpy_order_shard_parts(owned, first_sample, count, chunk, mean=None):
+    """One rank's part of ``numpy_order_sum`` over a raster of ``count`` samples: ``owned`` are its samples, the first of them
+    global sample ``first_sample``.  A dict: ``chunk_index`` / ``chunk_sums`` the global chunks wholly inside and their
+    pairwise sums, ``head`` / ``tail`` the fragments before the first and after the last chunk boundary with ``head_at`` /
+    ``tail_at`` their global offsets (samples with no boundary among them are all ``head``).  ``mean``: the same of the squared
+    deviations from it, the difference and the product each rounded to float32."""
+    values = np.ascontiguousarray(owned, dtype=np.float32).reshape(-1)
+    first, count, chunk = int(first_sample), int(count), int(chunk)
+    end = first + values.size
+    if first < 0 or end > count or chunk < 1:
+        raise ValueError(f"samples [{first}, {end}) of a raster of {count}, chunk {chunk}")
+    if mean is not None:
+        with np.errstate(all="ignore"):
+            dev = values - np.float32(mean)
+            values = dev * dev
+    c0, c1 = -(-first // chunk), end // chunk  # the first / one past the last global chunk boundary inside [first, end]
+    empty = np.zeros(0, dtype=np.float32)
+    if c0 > c1:  # no boundary inside: one fragment of one chunk
+        return {"chunk_index": np.zeros(0, dtype=np.int64), "chunk_sums": empty, "head": values, "head_at": first,
+                "tail": empty, "tail_at": end}
+    a, b = c0 * chunk - first, c1 * chunk - first
+    with np.errstate(all="ignore"):
+        sums = _pairwise_rows(values[a:b].reshape(c1 - c0, chunk)) if c1 > c0 else empty
+    return {"chunk_index": np.arange(c0, c1, dtype=np.int64), "chunk_sums": sums, "head": values[:a], "head_at": first,
+            "tail": values[b:], "tail_at": c1 * chunk}
+
+
+def numpy_order_combine(parts, count, chunk):
+    """``numpy_order_sum`` of the whole raster from every rank's ``numpy_order_shard_parts`` (in any order): full chunks
+    taken as summed, every other chunk put together from the fragments in sample order and summed pairwise, then the chain
+    from 0.  The parts must tile the raster's ``count`` samples."""
+    count, chunk = int(count), int(chunk)
+    total = -(-count // chunk)
+    sums = np.zeros(total, dtype=np.float32)
+    have = np.zeros(total, dtype=bool)
+    pieces = []
+    for p in parts:
+        index = np.asarray(p["chunk_index"], dtype=np.int64)
+        if have[index].any():
+            raise ValueError("numpy_order_combine: a chunk summed by two ranks")
+        sums[index] = p["chunk_sums"]
+        have[index] = True
+        pieces += [(int(p[k + "_at"]), np.asarray(p[k], dtype=np.float32)) for k in ("head", "tail") if len(p[k])]
+    pieces.sort(key=lambda piece: piece[0])
+    with np.errstate(all="ignore"):
+        for k in np.flatnonzero(~have):
+            lo, hi = k * chunk, min((k + 1) * chunk, count)
+            mine = [(at, v) for at, v in pieces if lo <= at < hi]
+            at = lo
+            for start, v in mine:
+                if start != at:
+                    break
+                at += v.size
+            if at != hi:
+                raise ValueError(f"numpy_order_combine: the parts do not tile samples [{lo}, {hi})")
+            sums[k] = _pairwise_rows(np.concatenate([v for _, v in mine])[None, :])[0]
+        return np.add.accumulate(np.concatenate([np.zeros(1, dtype=np.float32), sums]), dtype=np.float32)[-1]
+
+
+def numpy_order_moments_sharded(blocks, chunk=None):
+    """``numpy_order_moments`` of the raster whose consecutive row blocks are ``blocks``, from the blocks' parts alone: what a
+    row-sharded run gathers, with the bits of the whole raster's ``mean()`` / ``std()`` however the rows are cut."""
+    blocks = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
+    chunk = int(np.getbufsize()) if chunk is None else int(chunk)
+    firsts = np.concatenate([[0], np.cumsum([b.size for b in blocks])])
+    count = int(firsts[-1])
+    n = np.float32(count)
+    with np.errstate(all="ignore"):
+        parts = [numpy_order_shard_parts(b, f, count, chunk) for b, f in zip(blocks, firsts)]
+        mean = numpy_order_combine(parts, count, chunk) / n
+        parts = [numpy_order_shard_parts(b, f, count, chunk, mean=mean) for b, f in zip(blocks, firsts)]
+        return mean, np.sqrt(numpy_order_combine(parts, count, chunk) / n)
+
+
 _moments_checked = {}  # chunk -> whether this process's numpy sums as the model says
 
 

@@ -234,10 +234,29 @@ class ShardedDEM:
                                                       float(sigma), float(sig_ratio), mode,
                                                       _lib.ptr(rx), _lib.ptr(ry), *outs)
 
-    def valley_ridge(self, taps, ksize, angles, n_planes, norm, direction, sigma=None, moments=False):
+    def mean_std_numpy(self, chunk=None):
+        """Collective: ``(mean, std)`` of the WHOLE sharded raster as ``np.float32``, with the bits numpy's own ``a.mean()`` /
+        ``a.std()`` give for it on one host - and ``device.mean_std_numpy`` on one GPU - however the rows are cut
+        (``topo_amd_shard_mean_std_f32``; the model: ``helpers.numpy_order_moments_sharded``).  ``chunk``: numpy's buffer
+        size in samples (``np.getbufsize()``)."""
+        import ctypes as C
+
+        from . import _lib
+        p = self.plan
+        m, s = C.c_float(), C.c_float()
+        _lib.check(_lib.lib().topo_amd_shard_mean_std_f32(self.block.row_ptr(p.halo_above), p.rows_local, p.row0, p.gny, p.nx,
+                                                          int(np.getbufsize()) if chunk is None else int(chunk),
+                                                          C.byref(m), C.byref(s)), "topo_amd_shard_mean_std_f32")
+        return np.float32(m.value), np.float32(s.value)
+
+    def valley_ridge(self, taps, ksize, angles, n_planes, norm, direction, sigma=None, moments=False, numpy_moments=False):
         """Collective.  The plan's halo must be ``halo_rows(DESC_VALLEY_RIDGE, ksize.max(), sigma or 0)``; the mean
         and standard deviation of the whole DEM (with ``sigma``: of the whole smoothed DEM, topo.py:424-427) are formed
-        inside (one all-reduce).  ``moments=True``: returns the (mean, std) the call standardised with; otherwise None."""
+        inside (one all-reduce).  ``moments=True``: returns the (mean, std) the call standardised with; otherwise None.
+        ``numpy_moments``: False, the float64 moments (exact on whole metres); True, numpy's own float32 ``mean()`` /
+        ``std()`` of the whole raster, bit for bit for every sharding (``topo_amd_shard_valley_ridge_std`` with
+        ``helpers.moments_chunk()``), which makes the index the single GPU's ``Block(whole).valley_ridge(...)`` with no moments
+        passed (``topo_amd_valley_ridge_std_dev``) on the owned rows; an integer (not a bool) is taken as the chunk.  ``moments=True`` then returns the ``np.float32`` pair."""
         from . import _lib
         p = self.plan
         taps = np.ascontiguousarray(taps, dtype=np.float32)
@@ -245,6 +264,22 @@ class ShardedDEM:
         angles = np.ascontiguousarray(angles, dtype=np.float32)
         tables = (taps.ctypes.data_as(_lib._vp), ksize.ctypes.data_as(_lib._i32p), angles.ctypes.data_as(_lib._vp),
                   ksize.size, int(n_planes))
+        if numpy_moments is not False:
+            if numpy_moments is True:
+                from .helpers import moments_chunk
+                chunk = moments_chunk()
+                if chunk is None:
+                    raise RuntimeError("ShardedDEM.valley_ridge(numpy_moments=True): numpy's float32 moments cannot be formed on "
+                                       "the GPU here (TOPO_AMD_VALLEY_HOST_MOMENTS=1, a buffer size that is no power of two >= "
+                                       "128, or a numpy that does not sum as helpers.numpy_order_moments says); pass "
+                                       "numpy_moments=False for the float64 moments")
+            else:
+                chunk = int(numpy_moments)
+            sig = 0.0 if sigma is None else _sigma_value(sigma, "valley_ridge")
+            mom = np.zeros(2, dtype=np.float32)
+            self._collective("topo_amd_shard_valley_ridge_std", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, *tables,
+                             sig, chunk, norm.ptr, direction.ptr, mom.ctypes.data_as(_lib._f32p))
+            return (mom[0], mom[1]) if moments else None
         if sigma is None and not moments:
             self._collective("topo_amd_shard_valley_ridge", self.block.ptr, p.rows_local, p.row0, p.gny, p.nx, *tables,
                              norm.ptr, direction.ptr)
