@@ -688,7 +688,7 @@ def test_widths_that_are_not_multiples_of_four(nx, size):
 
 def test_gradient_row_chunks_bit_identical(tmp_path):
     """From 8192 rows on, the matrix-core gradient goes in row chunks with the epilogue of a chunk on a second
-    stream beside the smooth of the next one (csrc/gauss.hip launch_gradient).  Chunks are row blocks: the bits
+    stream beside the smooth of the next one (csrc/gradient.hip launch_gradient).  Chunks are row blocks: the bits
     must not depend on the cut.  The threshold is read once per process, hence two child processes."""
     import subprocess
     import sys

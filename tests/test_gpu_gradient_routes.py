@@ -1,4 +1,4 @@
-"""The gradient (csrc/gauss.hip, ``launch_gradient``) on every kernel route, all four planes held to float64.
+"""The gradient (csrc/gradient.hip, ``launch_gradient``) on every kernel route, all four planes held to float64.
 
 ``launch_gradient`` picks Sobel / Chunked / Mfma / Valu / Aniso, under that a fused f16 kernel (4, 6 or 8 steps), the two-pass
 tile kernels or the split-once axis 1 (NK 5 / 7 / 9), on the vector-ALU route the LDS-tiled axis-1 + epilogue kernel (tap
@@ -102,7 +102,7 @@ NON_FINITE = ("sobel_s", "fused4_r5", "fused8_r33", "tile_r48", "split5_r49", "c
 BLOCK_OUT = (128, 228)  # "block": output rows [128, 228) of 300 with the fewest ghost rows the library takes, radius + 1
 #                         (test_the_block_case_carries_the_fewest_ghost_rows): device rows [114, 242) at radius 13, so the
 #                         accumulation-offset row 112 of the first 32-row tile is not in the block
-# the first and the last cut between the row chunks of the chunked cases (csrc/gauss.hip, gradient_chunked; the route pins
+# the first and the last cut between the row chunks of the chunked cases (csrc/gradient.hip, gradient_chunked; the route pins
 # the number of chunks and the taper): chunks of 544 / 704 rows, tapered 512 + 4 x 2816 + 512 and 1024 + 2 x 7168 + 1024
 CHUNK_CUTS = {"chunk_fused": (544, 1632), "chunk_tile": (704, 1408), "taper_fused": (512, 11776), "taper_tile": (1024, 15360)}
 

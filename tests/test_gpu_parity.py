@@ -327,6 +327,40 @@ def test_gaussian_split_once_axis1(sigma):
             assert np.max(np.abs(g - t)) <= 1e-3 and not np.array_equal(g, t)  # (another kernel did run)
 
 
+def test_gaussian_every_step_count():
+    """One radius per step count of the matrix-core tile kernels (4, 17, 33, 50, 80, 88, 104, 121: 4 ... 18 steps of 16
+    samples), both passes, axis 0 alone and axis 1 alone, against the float64 filter: here (axis 1 from 10 steps on the
+    split-once kernel) and in one child process with TOPO_AMD_GAUSS_SPLIT_ONCE=0 (the tile kernels on both axes).  The
+    shapes give partial 32-row bands and partial tiles; (37, 100) is narrower than the widest window."""
+    import subprocess, sys, tempfile
+    sigmas = [1.0, 4.25, 8.25, 12.5, 20.0, 22.0, 26.0, 30.25]
+    shapes = [(129, 321), (37, 100)]
+    cases = [(k, s, mode) for k in range(len(shapes)) for s in sigmas for mode in ("both", "axis0", "axis1")]
+    arg = {"both": lambda s: s, "axis0": lambda s: (s, 0.0), "axis1": lambda s: (0.0, s)}
+    dems = [orc.synthetic_dem(ny, nx, seed=90 + k) for k, (ny, nx) in enumerate(shapes)]
+    want = [orc.gaussian_exact(dems[k], arg[mode](s)) for k, s, mode in cases]
+    here = [topo.dem(dems[k], arg[mode](s)) for k, s, mode in cases]
+    with tempfile.TemporaryDirectory() as tmp:
+        code = (
+            "import sys, numpy as np\n"
+            "sys.path.insert(0, %r)\n"
+            "from topo_descriptors_amd import topo\n"
+            "from oracle import topo_oracle as orc\n"
+            "shapes, sigmas = %r, %r\n"
+            "dems = [orc.synthetic_dem(ny, nx, seed=90 + k) for k, (ny, nx) in enumerate(shapes)]\n"
+            "np.savez(%r, *[topo.dem(dems[k], a) for k in range(len(shapes)) for s in sigmas for a in (s, (s, 0.0), (0.0, s))])\n"
+        ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), shapes, sigmas, os.path.join(tmp, "tile.npz"))
+        subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, TOPO_AMD_GAUSS_SPLIT_ONCE="0"))
+        tile = np.load(os.path.join(tmp, "tile.npz"))
+        child = [tile["arr_%d" % n] for n in range(len(cases))]
+    errs = {}
+    for (k, s, mode), w, g, t in zip(cases, want, here, child):
+        errs[(shapes[k], s, mode)] = (float(np.max(np.abs(g.astype(np.float64) - w))), float(np.max(np.abs(t.astype(np.float64) - w))))
+        print("gaussian", shapes[k], "sigma", s, mode, "max error: %.3g here, %.3g tile kernels" % errs[(shapes[k], s, mode)])
+    worst = {key: e for key, e in errs.items() if max(e) > 1e-3}
+    assert not worst, worst
+
+
 def test_gaussian_turned_tile_order_against_the_float64_filter():
     """The axis-1 matrix-core kernels (fused, tile, split-once) let every band / row block walk its row from a tile of its own
     (no lockstep over the columns: profiles/r04_pitch_spread.txt); a run that meets the end of the row goes on at its start.

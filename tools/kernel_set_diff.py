@@ -3,7 +3,11 @@ machine code, and whether a kernel both builds hold has the same bytes over its 
 
 usage: kernel_set_diff.py OLD/topo_descriptors_amd/build NEW/topo_descriptors_amd/build [unit-prefix ...]
 (unit prefixes default to the disc units: disc_wave_group disc_pair disc_wave).  Exit status 1 when NEW holds a kernel OLD
-does not, or a kernel of both differs."""
+does not, or a kernel of both differs.
+
+       kernel_set_diff.py --symbols OLD/.../build NEW/.../build [unit-prefix ...]
+pairs kernels by name across all objects of each build directory (with prefixes: across the objects they select in
+either), so a kernel that moved from one unit to another is compared with itself.  Same rules, same exit status."""
 import os
 import shutil
 import struct
@@ -52,15 +56,41 @@ def without_pc_offsets(code):
     return words
 
 
+def demangled(names):
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt", path=LLVM)
+    if not filt or not names:
+        return list(names)
+    return subprocess.run([filt], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")[:len(names)]
+
+
+def pooled(build_dir, prefixes, tmp):
+    """{kernel: its machine code} over every object of ``build_dir`` whose name starts with one of ``prefixes``.  A kernel is
+    named by its demangled symbol without the ``(anonymous namespace)::`` qualifiers: they stand for the unit, and differ
+    between two builds when a kernel, or the type of one of its arguments, has moved to another unit or into a header."""
+    pool = {}
+    for unit in sorted(f for f in os.listdir(build_dir) if f.endswith(".o") and f.startswith(prefixes)):
+        ks = kernels(os.path.join(build_dir, unit), tmp)
+        for symbol, name in zip(ks, demangled(list(ks))):
+            name = name.replace("(anonymous namespace)::", "")
+            if name in pool and without_pc_offsets(pool[name]) != without_pc_offsets(ks[symbol]):
+                name += f" [another one in {unit}]"  # (a template instance two units build is one kernel)
+            pool.setdefault(name, ks[symbol])
+    return pool
+
+
 def main():
-    old_dir, new_dir = sys.argv[1:3]
-    prefixes = tuple(sys.argv[3:]) or ("disc_wave_group", "disc_pair", "disc_wave")
-    units = sorted(f for f in os.listdir(old_dir) if f.endswith(".o") and f.startswith(prefixes))
+    by_symbol = sys.argv[1] == "--symbols"
+    old_dir, new_dir = sys.argv[1 + by_symbol:3 + by_symbol]
+    prefixes = tuple(sys.argv[3 + by_symbol:]) or (("",) if by_symbol else ("disc_wave_group", "disc_pair", "disc_wave"))
+    units = ["all objects"] if by_symbol else sorted(f for f in os.listdir(old_dir) if f.endswith(".o") and f.startswith(prefixes))
     total = {"old": [0, 0], "new": [0, 0]}
     added, changed, moved, removed = [], [], [], []
     with tempfile.TemporaryDirectory() as tmp:
         for unit in units:
-            old, new = kernels(os.path.join(old_dir, unit), tmp), kernels(os.path.join(new_dir, unit), tmp)
+            if by_symbol:
+                old, new = pooled(old_dir, prefixes, tmp), pooled(new_dir, prefixes, tmp)
+            else:
+                old, new = kernels(os.path.join(old_dir, unit), tmp), kernels(os.path.join(new_dir, unit), tmp)
             for key, ks in (("old", old), ("new", new)):
                 total[key][0] += len(ks)
                 total[key][1] += sum(len(code) for code in ks.values())

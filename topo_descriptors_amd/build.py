@@ -10,15 +10,16 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtopo_amd.so")
 NGROUPS = 16  # the per-size disc kernels: one source (disc_wave_group.hip), compiled once per group of sizes
 # (source, extra flags, object name); the long units first, so that the pool's last jobs are short ones
-UNITS = [("sx.hip", [], "sx.o"), ("gauss.hip", [], "gauss.o"), ("host_api.hip", [], "host_api.o"), ("shard.hip", [], "shard.o")] + \
+UNITS = [("sx.hip", [], "sx.o"), ("gauss_f16.hip", [], "gauss_f16.o"), ("host_api.hip", [], "host_api.o"), ("shard.hip", [], "shard.o")] + \
         [("disc_wave_group.hip", [f"-DTOPO_GROUP={g}", f"-DTOPO_NGROUPS={NGROUPS}"], f"disc_wave_group{g}.o") for g in range(NGROUPS)] + \
-        [(s, [], s.replace(".hip", ".o")) for s in ("disc_pair.hip", "disc.hip", "disc_wave.hip", "disc_big.hip", "valley.hip",
+        [(s, [], s.replace(".hip", ".o")) for s in ("disc_pair.hip", "disc.hip", "disc_wave.hip", "disc_big.hip", "gradient.hip",
+                                                    "gauss.hip", "valley.hip",
                                                     "moments_np.hip",
                                                     "valley_mfma.hip", "valley_fft.hip", "fill.hip", "decode.hip", "encode.hip",
                                                     "finish.hip", "raster_class.hip", "context.hip", "capi.hip")]
 SOURCES = sorted({u[0] for u in UNITS})
 ARCH = "gfx950"
-FLAGS = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
+FLAGS = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall"]
 
 
 def hipcc():

@@ -162,7 +162,7 @@ void dem_memo_forget(const void* p, size_t bytes) {
 // The lattice belongs to the GLOBAL grid: rows step_r / 2 + i step_r, columns step_c / 2 + j step_c with step = extent / 128
 // (about 16 K points), so the scans of the row blocks of a raster add up to the scan of the whole raster, point for point.
 namespace {
-constexpr float kClassLarge = 1.0e5f;     // kWild of gauss.hip: what the f16 matrix-core kernels stage as 0 and repair
+constexpr float kClassLarge = 1.0e5f;     // kWild of gauss_f16.hip: what the f16 matrix-core kernels stage as 0 and repair
 constexpr float kClassOrdinary = 262144.0f;  // kAbsLim of the disc kernels
 inline int lattice_step(int extent) { return std::max(1, extent / 128); }
 __device__ __forceinline__ uint32_t ordered_bits(float f) {  // unsigned order = float order (finite values)
