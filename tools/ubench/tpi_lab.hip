@@ -11,6 +11,8 @@
 //   (-DMARCH_DYN_ROWS=0/1, -DCHAIN_PRIO=0/1, -DMARCH_STAMPS)
 //   -DWIDE_STAMPS=1/2 (variant any_tpi): clock stamps of tpi_ring_wide_kernel<67> at the end of a phase, printed per wave for
 //   two blocks - 1 with the chain waves' output stores drained in front of the barrier, 2 without (the kernel as built)
+//   -DWIDE_STAGE_CEILING=1 (variant any_tpi): tpi_ring_wide_kernel<67> whose staging only converts, prefixes and writes, flags
+//   constant 0 (whole-metre rasters only: the ceiling of a leaner staging stream); -DWIDE_LEAN=0: every batch on the general path
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

@@ -13,14 +13,16 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r10_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r11_tpi67_wide_valu_count.json
 
 wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
 row loop per VALID output column: offline, before any GPU time.  A chain wave sums its two rows of a phase in one sweep
 (55 distinct prefix rows of three ds_read_b64 for the pair), so the count is that of the chain waves' phase loop - the
 sweep, the finalisation and the stores of both rows, the barrier - and an output row is half of it.  Vector adds whose
-result is a ds_read address are counted as their own class.
+result is a ds_read address are counted as their own class.  The staging waves' phase loop is reported beside it
+(staging_phase_loop): every instruction the loop holds, and the way round it that an interior batch takes (the lean path of
+stage_batch and load_batch) - instructions, VALU by opcode, scalar instructions, branches, the VALU's price.
 
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
@@ -109,6 +111,83 @@ def price(o):
     return valu, kinds, mix["plain"] * NS_PLAIN + mix["half"] * NS_HALF
 
 
+def blocks_of(lines):
+    """Basic blocks of a loop body (instruction lines and labels, in order): [label or None, [instructions]]."""
+    out = [[None, []]]
+    for x in lines:
+        x = x.strip()
+        m = re.match(r"^(\.LBB\d+_\d+):", x)
+        if m:
+            out.append([m.group(1), []])
+        elif x and not x.startswith((".", ";", "//")):
+            out[-1][1].append(x)
+            if x.startswith(("s_cbranch", "s_branch")):
+                out.append([None, []])
+    return [b for b in out if b[0] or b[1]]
+
+
+def rows_written(mn):
+    """Ring rows a list of mnemonics writes: a ds_write2(st64)_b64 carries two."""
+    return mn.count("ds_write_b64") + 2 * sum(1 for x in mn if x.startswith("ds_write2") and x.endswith("_b64"))
+
+
+def staging_loop(txt):
+    """The staging waves' phase loop of the wide kernel: the smallest loop that loads a batch (16 global_load_dwordx2) and
+    writes it (16 ds_write_b64), meets the phase barrier and has no float64 (the run's prologue stages batches in a loop of its
+    own, with no barrier in it).  Returns (all its instructions, the shortest way round it that still
+    loads and writes a batch: the lean path of an interior batch, with no guard copies and no phase that is not computed)."""
+    start = txt.index(WIDE_KERNEL + SUFFIX)
+    lines = txt[start:txt.index("s_endpgm", start)].split("\n")
+    labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
+    best = None
+    for i, l in enumerate(lines):
+        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.search(r"s_branch\s+(\.LBB\d+_\d+)", l)
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            body = lines[labels[m.group(1)]:i + 1]
+            mn = [x.split()[0] for x in body if x.strip() and not x.strip().startswith((".", ";", "//")) and not x.strip().endswith(":")]
+            if (mn.count("global_load_dwordx2") >= 16 and rows_written(mn) >= 16 and "s_barrier" in mn
+                    and not any("f64" in x for x in mn) and (best is None or len(body) < len(best))):
+                best = body
+    assert best is not None, "no staging phase loop found"
+    bl = blocks_of(best)
+    at = {b[0]: k for k, b in enumerate(bl) if b[0]}
+    shortest = [None]
+
+    def walk(k, path, seen):
+        while True:
+            if k >= len(bl):
+                return
+            path = path + bl[k][1]
+            seen = seen | {k}
+            last = bl[k][1][-1] if bl[k][1] else ""
+            tgt = (last.split()[1] if last.startswith(("s_cbranch", "s_branch")) else None)
+            if k == len(bl) - 1:  # the back edge
+                mn = [x.split()[0] for x in path]
+                if mn.count("global_load_dwordx2") >= 16 and rows_written(mn) >= 16 and (shortest[0] is None or len(path) < len(shortest[0])):
+                    shortest[0] = path
+                return
+            if tgt is not None and tgt in at and at[tgt] > k and at[tgt] not in seen:
+                walk(at[tgt], path, seen)
+            if last.startswith("s_branch"):
+                return
+            k += 1
+
+    walk(0, [], frozenset())
+    assert shortest[0] is not None, "no way round the staging loop that loads and writes a batch"
+    return [x for b in bl for x in b[1]], shortest[0]
+
+
+def staging_report(lines):
+    mn = [x.split()[0] for x in lines]
+    valu, kinds, ns = price(mn)
+    return {"instructions": len(mn), "valu": len(valu), "valu_half_rate": sum(1 for x in valu if half_rate(x)),
+            "valu_by_op": dict(Counter(valu).most_common()), "salu": sum(1 for x in mn if x.startswith("s_")),
+            "salu_by_op": dict(Counter(x for x in mn if x.startswith("s_")).most_common()),
+            "branches": sum(1 for x in mn if x.startswith(("s_cbranch", "s_branch"))),
+            "global_load_dwordx2": mn.count("global_load_dwordx2"), "ring_rows_written": rows_written(mn),
+            "valu_ns": round(ns, 1)}
+
+
 def wide():
     csrc = os.path.join(REPO, "topo_descriptors_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
@@ -132,8 +211,44 @@ def wide():
     # (round 10: the staging waves' last loads, open where the two paths meet, put four such waits there)
     vm_waits = [i for i, x in enumerate(ph) if x.startswith("s_waitcnt") and "vmcnt" in x]
     assert not vm_waits, f"the chain waves' phase loop waits for its output stores at instructions {vm_waits}"
+    # nor may it grow: at most 812 VALU a pair (810 with the shared band sums alone; a scalar register that the staging
+    # path's pressure pushes into a VGPR lane comes back here as a v_readlane, which is VALU and is reported beside the count)
+    reloads = sum(x.startswith(("v_readlane", "v_writelane")) for x in mn)
+    assert sum(x.startswith("v_") for x in mn) <= 812, f"the chain waves' phase loop grew ({reloads} reloads of spilled scalar registers in it)"
     row = ph
     o = mn
+    # the staging waves' phase loop, and within it the lean path of an interior batch: its rows - from the first load to the
+    # last, and from the first convert to the last ring write - are straight-line code with no select, no multiplication
+    # and no 64-bit vector address (the one multiplication the scheduler may put among the rows is the batch's: its first
+    # slot times the ring's row pitch of 0x600 bytes)
+    st_all, st_lean = staging_loop(txt)
+    lm = [x.split()[0] for x in st_lean]
+    loads = [i for i, x in enumerate(lm) if x == "global_load_dwordx2"]
+    first_cvt = lm.index("v_cvt_i32_f32_e32")
+    last_write = max(i for i, x in enumerate(lm) if x.startswith("ds_write"))
+    for name, (a, b) in {"loads": (loads[0], loads[-1]), "rows": (first_cvt, last_write)}.items():
+        inside = lm[a:b + 1]
+        assert not any(x.startswith(("s_cbranch", "s_branch")) for x in inside), f"lean path: a branch among the batch's {name}"
+        muls = [x for x in st_lean[a:b + 1] if x.startswith(("s_mul", "v_mul", "v_mad"))]
+        assert all(x.startswith("s_mul_i32") and x.endswith("0x600") for x in muls) and len(muls) <= (1 if name == "rows" else 0), \
+            f"lean path: a multiplication per row among the batch's {name}: {muls}"
+        assert "v_lshl_add_u64" not in inside, f"lean path: a 64-bit vector address among the batch's {name}"
+    assert not any(x.startswith("v_cndmask") for x in lm[first_cvt:last_write + 1]), "lean path: a select among the batch's rows"
+    # The batch's branches, apart from the phase's own.  The staging of a batch comes first in a phase, then lane 0's store
+    # of the flags (the one branch on the exec mask), then the next batch's loads, then the barrier; what follows the barrier
+    # is the loop's.  In the source a batch makes three choices - lean or general staging, guard copies or none, interior
+    # rows or not for the loads - and the compiler lays each two-sided choice out as the general block under one branch and
+    # the lean block under a second one on a flag the first side sets: 2 + 1 branches for the staging, 2 for the loads.
+    # (One branch per choice, two or three a batch, is what the source asks for; the second branch of a pair is the compiler's.)
+    cond = [i for i, x in enumerate(lm) if x.startswith("s_cbranch")]
+    flag_store = [i for i in cond if lm[i] == "s_cbranch_execz"]
+    assert len(flag_store) == 1 and "s_barrier" in lm, "lean path: lane 0's flag store and the phase barrier mark the batch's parts"
+    barrier = lm.index("s_barrier")
+    assert last_write < flag_store[0] < loads[0] and loads[-1] < barrier, "lean path: staging, flag store, loads, barrier in this order"
+    stage_branches = sum(1 for i in cond if i < flag_store[0])
+    load_branches = sum(1 for i in cond if flag_store[0] < i < barrier)
+    assert stage_branches <= 3, f"lean path: {stage_branches} branches for a batch's staging (lean or general twice, guard copies)"
+    assert load_branches <= 2, f"lean path: {load_branches} branches for a batch's loads (interior rows or not, twice)"
     n_addr = address_adds(row)
     om = loop_ops(txt_m, KERNEL, lambda o: 42 <= sum(x == "ds_read_b128" for x in o) <= 46 and any("f64" in x for x in o))
     valu, kinds, ns = price(o)
@@ -142,7 +257,7 @@ def wide():
     kinds["ds_read_address"] = n_addr
     pair = {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b64": o.count("ds_read_b64"), "s_nop": o.count("s_nop"),
             "salu": sum(1 for x in o if x.startswith("s_")), "global_store_dwordx2": o.count("global_store_dwordx2"),
-            "vmcnt_waits": len(vm_waits), "instructions": len(o), "ns": round(ns, 1)}
+            "vmcnt_waits": len(vm_waits), "sgpr_reloads": reloads, "instructions": len(o), "ns": round(ns, 1)}
     # per output row: half the pair
     valu = valu[:len(valu) // 2]
     kinds = Counter({k: v / 2 for k, v in kinds.items()})
@@ -151,6 +266,8 @@ def wide():
     print(json.dumps({
         "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns): half the row pair of the phase loop",
         "row_pair_instructions": pair,
+        "staging_phase_loop": {"whole_loop": staging_report(st_all),
+                               "lean_path": dict(staging_report(st_lean), batch_branches={"staging": stage_branches, "loads": load_branches})},
         "row_loop_instructions": {"valu": pair["valu"] / 2, "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128") / 2,
                                   "ds_read_b64": o.count("ds_read_b64") / 2, "v_mov_b32_dpp": o.count("v_mov_b32_dpp") / 2,
                                   "s_nop": o.count("s_nop") / 2, "salu": sum(1 for x in o if x.startswith("s_")) / 2},

@@ -15,7 +15,8 @@
 //     67 px where two single rows read 84, and each is read once;
 //   * the staging runs on waves of its own (std_ring_spec_kernel's structure):
 //     waves 0-2 convert, classify and write batch ph + 1 (16 rows, two columns per lane, 8-byte loads) and issue the
-//     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase;
+//     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase; a batch whose rows,
+//     columns and slots need no test, clamp or wrap (wave-uniform: nearly all of them) takes a lean path of its own;
 //   * prefix sums are uint32 modulo 2^32 with no offset and the finalisation is tpi_march_kernel's expression, so the
 //     bits are those of the marching kernel.
 //
@@ -199,12 +200,19 @@ __device__ __forceinline__ void wide_static_for(F&& f) {
 // The joint sweep's order of sums: the runs in the order WGeo::S.order, the lane's columns s = 0 .. NCW - 1 of each.
 // firstR[D][t] (firstL) is j NCW + s of the first difference that goes into step D of the right (left) chain for output
 // t - the one that starts the sum - or -1 where the lane's own columns give that step nothing.
+// lo_s[j][side][D][t] .. hi_s[j][side][D][t] (side 0 right, 1 left) are the first and last column s of the lane whose tap
+// for that sum belongs to fetch j's run (lo_s > hi_s: none).  A run's columns on one side of the centre are adjacent, so
+// the taps of a sum within a run are ONE interval of s, and the sweep adds the interval's sum, not its members.
 template <int SIZE>
 struct WSweep {
     using G = WGeo<SIZE>;
     struct Tab {
         int firstR[G::DL + 1][NCW], firstL[G::DL + 1][NCW];
+        int lo_s[G::NR][2][G::DL + 1][NCW], hi_s[G::NR][2][G::DL + 1][NCW];
     };
+    // the disc offset of column s of the lane in step D of the chain of `side` for output t, and whether that side takes it
+    static constexpr int tap(int side, int D, int s, int t) { return (side == 0 ? NCW * D : -NCW * D) + s - t; }
+    static constexpr bool takes(int side, int di) { return side == 0 ? di >= 0 && di <= G::M : di < 0 && di >= -G::M; }
     static constexpr Tab make() {
         Tab t{};
         for (int D = 0; D <= G::DL; ++D)
@@ -217,9 +225,63 @@ struct WSweep {
                         if (dr >= 0 && dr <= G::M && G::T.run_of[dr - G::T.off_min] == G::S.order[j]) t.firstR[D][o] = j * NCW + s;
                         if (dl < 0 && dl >= -G::M && G::T.run_of[dl - G::T.off_min] == G::S.order[j]) t.firstL[D][o] = j * NCW + s;
                     }
+        for (int j = 0; j < G::NR; ++j)
+            for (int side = 0; side < 2; ++side)
+                for (int D = 0; D <= G::DL; ++D)
+                    for (int o = 0; o < NCW; ++o) {
+                        int lo = NCW, hi = -1;
+                        for (int s = 0; s < NCW; ++s) {
+                            const int di = tap(side, D, s, o);
+                            if (takes(side, di) && G::T.run_of[di - G::T.off_min] == G::S.order[j]) {
+                                lo = s < lo ? s : lo;
+                                hi = s;
+                            }
+                        }
+                        t.lo_s[j][side][D][o] = lo;
+                        t.hi_s[j][side][D][o] = hi;
+                    }
         return t;
     }
     static constexpr Tab T = make();
+    // over all runs the intervals take every (offset, output) pair with |offset| <= M exactly once
+    static constexpr bool covers() {
+        int hits[NCW][2 * G::M + 1] = {};
+        int total = 0;
+        for (int j = 0; j < G::NR; ++j)
+            for (int side = 0; side < 2; ++side)
+                for (int D = 0; D <= G::DL; ++D)
+                    for (int o = 0; o < NCW; ++o)
+                        for (int s = T.lo_s[j][side][D][o]; s <= T.hi_s[j][side][D][o]; ++s) {
+                            const int di = tap(side, D, s, o);
+                            if (di < -G::M || di > G::M) return false;
+                            ++hits[o][di + G::M];
+                            ++total;
+                        }
+        for (int o = 0; o < NCW; ++o)
+            for (int d = 0; d <= 2 * G::M; ++d)
+                if (hits[o][d] != 1) return false;
+        return total == NCW * (2 * G::M + 1);
+    }
+    // the difference that starts a sum is the first column of an interval, and no interval lies before it
+    static constexpr bool firsts_start_intervals() {
+        for (int side = 0; side < 2; ++side)
+            for (int D = 0; D <= G::DL; ++D)
+                for (int o = 0; o < NCW; ++o) {
+                    const int f = side == 0 ? T.firstR[D][o] : T.firstL[D][o];
+                    for (int j = 0; j < G::NR; ++j) {
+                        const bool empty = T.lo_s[j][side][D][o] > T.hi_s[j][side][D][o];
+                        if (f < 0 || j < f / NCW) {
+                            if (!empty) return false;
+                        } else if (j == f / NCW) {
+                            if (empty || T.lo_s[j][side][D][o] != f % NCW) return false;
+                        }
+                    }
+                }
+        return true;
+    }
+    static_assert(covers(), "the intervals take every tap of every output once: SIZE taps an output");
+    static_assert(SIZE != 67 || NCW * (2 * G::M + 1) == 402, "67 px: 402 taps per side pair");
+    static_assert(firsts_start_intervals(), "firstR / firstL name an interval's first column");
     // issue priority over the steps DL ... 0: 3 at the first, 0 at the last
     static constexpr int prio_of(int D) { return 3 - (G::DL - D) * 4 / (G::DL + 1); }
 };
@@ -239,6 +301,16 @@ struct WSweep {
 #ifndef WIDE_STAMPS
 #define WIDE_STAMPS 0
 #endif
+// (lab switch: 0 stages every batch on the general path, the kernel of rounds 7 - 10, for an A/B against the lean path)
+#ifndef WIDE_LEAN
+#define WIDE_LEAN 1
+#endif
+// (lab switch: 1 leaves the classification out of stage_batch - convert, prefix, write, flags constant 0 - on both of its
+// paths: what the staging waves' stream could shrink to at the most.  Right on rasters of whole metres only, where every
+// window is computed anyway.  tools/ubench/tpi_lab.hip -DWIDE_STAGE_CEILING=1, profiles/r11_tpi67_staging_ceiling.txt)
+#ifndef WIDE_STAGE_CEILING
+#define WIDE_STAGE_CEILING 0
+#endif
 #if WIDE_STAMPS
 constexpr int kWideStampBlocks = 2, kWideStampWaves = 11, kWideStampFields = 5;
 // per stamped block and wave: phases, ticks in all of them, in the drain, at the barrier, in a back-to-back stamp pair
@@ -252,6 +324,7 @@ __device__ __forceinline__ uint32_t wide_now() {  // (the low word: a phase is a
 
 typedef uint32_t u32x2w __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const char lds_char;
+typedef __attribute__((address_space(1))) const u32x2w glb_u32x2w;
 typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 
 // Disc sums of the two output rows of a chain wave in ONE sweep (ring_disc_sum with 6 columns per lane, two rows): s0 is
@@ -353,33 +426,39 @@ __device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, int s0, int 
         if constexpr (PRIO && SW_::prio_of(D) != SW_::prio_of(Dprev)) CHAIN_SETPRIO(SW_::prio_of(D));
         if constexpr (j + LEAD < NR) fetch(std::integral_constant<int, j + LEAD>{});
         RING_SB();
-        wide_static_for<NCW>([&](auto S) {
-            constexpr int s = decltype(S)::value;
-            uint32_t cv[2];
+        // the differences of the run for the lane's six columns of both rows, their prefix and suffix sums over s (the
+        // compiler drops the ones no interval asks for), then every (side, step, output) sum takes its interval in one add
+        uint32_t cv[2][NCW], pre[2][NCW], suf[2][NCW];
 #pragma unroll
-            for (int w = 0; w < 2; ++w) {
-                cv[w] = row[PT::T.use[j][w][0]][s / 2][s % 2] - row[PT::T.use[j][w][1]][s / 2][s % 2];
-                if (r == G::S.centre_run) ctr[w][s] = cv[w];
+        for (int w = 0; w < 2; ++w) {
+#pragma unroll
+            for (int s = 0; s < NCW; ++s) {
+                cv[w][s] = row[PT::T.use[j][w][0]][s / 2][s % 2] - row[PT::T.use[j][w][1]][s / 2][s % 2];
+                if (r == G::S.centre_run) ctr[w][s] = cv[w][s];
             }
-            // every (step, output) that takes column s of run r: of this step and of the later ones
-            wide_static_for<(DL + 1) * NCW>([&](auto ET) {
-                constexpr int E = decltype(ET)::value / NCW, t = decltype(ET)::value % NCW;
-                constexpr int dr = NCW * E + s - t, dl = -NCW * E + s - t;
-                if constexpr (dr >= 0 && dr <= M) {
-                    if constexpr (G::T.run_of[dr - G::T.off_min] == r) {
-                        static_assert(E <= D, "a run arrives at the first step that takes it");
+            pre[w][0] = cv[w][0];
+            suf[w][NCW - 1] = cv[w][NCW - 1];
 #pragma unroll
-                        for (int w = 0; w < 2; ++w) pR[w][E][t] = SW_::T.firstR[E][t] == j * NCW + s ? cv[w] : pR[w][E][t] + cv[w];
-                    }
-                }
-                if constexpr (dl < 0 && dl >= -M) {
-                    if constexpr (G::T.run_of[dl - G::T.off_min] == r) {
-                        static_assert(E <= D, "a run arrives at the first step that takes it");
+            for (int s = 1; s < NCW; ++s) {
+                pre[w][s] = pre[w][s - 1] + cv[w][s];
+                suf[w][NCW - 1 - s] = suf[w][NCW - s] + cv[w][NCW - 1 - s];
+            }
+        }
+        wide_static_for<2 * (DL + 1) * NCW>([&](auto ET) {
+            constexpr int side = decltype(ET)::value / ((DL + 1) * NCW);
+            constexpr int E = decltype(ET)::value / NCW % (DL + 1), t = decltype(ET)::value % NCW;
+            constexpr int a = SW_::T.lo_s[j][side][E][t], b = SW_::T.hi_s[j][side][E][t];
+            if constexpr (a <= b) {
+                static_assert(E <= D, "a run arrives at the first step that takes it");
+                constexpr bool starts = (side == 0 ? SW_::T.firstR[E][t] : SW_::T.firstL[E][t]) / NCW == j;
 #pragma unroll
-                        for (int w = 0; w < 2; ++w) pL[w][E][t] = SW_::T.firstL[E][t] == j * NCW + s ? cv[w] : pL[w][E][t] + cv[w];
-                    }
+                for (int w = 0; w < 2; ++w) {
+                    const uint32_t iv = a == b ? cv[w][a] : a == 0 ? pre[w][b] : b == NCW - 1 ? suf[w][a] :
+                                        b == a + 1 ? cv[w][a] + cv[w][b] : pre[w][b] - pre[w][a - 1];
+                    uint32_t& acc_p = side == 0 ? pR[w][E][t] : pL[w][E][t];
+                    acc_p = starts ? iv : acc_p + iv;
                 }
-            });
+            }
         });
         RING_SB();
         // the steps no later run opens: closed here
@@ -435,10 +514,42 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         const int gcol = gx0 + scol;  // even, and nx % 4 == 0: the lane's two columns are both inside or both outside
         const bool col_ok = stager && gcol >= 0 && gcol < p.nx;
         const float* src = p.in + (col_ok ? gcol : 0);
+        // A batch is INTERIOR when its B rows all lie in the raster; the staging takes it on a lean path when, besides, every
+        // lane of the wave has its columns in the raster and the batch's slots do not wrap the ring: wave-uniform conditions,
+        // one branch a batch, and then no row needs a clamp, a test, a multiplication or a slot wrap of its own.  On the
+        // bench DEM that is every batch but a run's first and last ones and the last strip's.
+        // (The lean path leans on three empty asm statements that only hold the optimiser back: the opaque row base and the
+        // statement behind the loads in load_batch, the folding point of the compare masks in stage_batch.  What they buy is
+        // a property of the compiled code, not of the source: after a compiler update run tools/valu_bound.py wide and
+        // tools/spill_survey.py tpi_ring_wide_kernel again - the tool asserts the loads' form, the rows without branch,
+        // select or multiplication, and the size of the chain waves' loop, reloads of spilled registers included.)
+        constexpr bool kLean = WIDE_LEAN || WIDE_STAGE_CEILING;
+        const bool cols_in = kLean && __builtin_amdgcn_ballot_w64(col_ok) == ~0ull;
+        const uint32_t voff = (uint32_t)(col_ok ? gcol : 0) * 4u;
         auto load_batch = [&](int n0, float2 (&v)[B]) {
+            const int g0 = gy0 + n0;
+            if (kLean && g0 >= rmin && g0 + B <= rmax && p.nx < (1 << 29)) {  // (a lane's byte offset in a row: 32 bits)
+                // interior rows: one scalar row base a batch that runs on by the pitch, the lane's offset beside it.  (The base
+                // is opaque in every row: the address stays scalar base + 32-bit lane offset, which is the load's own form,
+                // where the compiler would hoist base + lane offset as a 64-bit vector and add the rows to that.)
+                uint64_t rowa = reinterpret_cast<uint64_t>(p.in) + (uint64_t)(g0 - p.in_row0) * (uint64_t)p.nx * sizeof(float);
+                uint32_t vo = voff;
+                asm("" : "+v"(vo));
+#pragma unroll
+                for (int r = 0; r < B; ++r) {
+                    asm("" : "+s"(rowa));
+                    const u32x2w t = *reinterpret_cast<glb_u32x2w*>(rowa + vo);
+                    v[r] = make_float2(__uint_as_float(t.x), __uint_as_float(t.y));
+                    rowa += (uint64_t)p.nx * sizeof(float);
+                }
+                // (the compiler would sink these loads into one block with the general path's below, behind a 64-bit vector
+                // address for each: with this in their way they stay here, scalar base and 32-bit lane offset)
+                asm volatile("");
+                return;
+            }
 #pragma unroll
             for (int r = 0; r < B; ++r) {
-                int gy = gy0 + n0 + r;
+                int gy = g0 + r;
                 gy = min(max(gy, rmin), rmax - 1);  // a clamped row is read and thrown away
                 v[r] = *reinterpret_cast<const float2*>(src + (size_t)(gy - p.in_row0) * p.nx);
             }
@@ -451,32 +562,67 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         const uint32_t kLimBits = __float_as_uint(kAbsLim + 1.0f);  // |trunc(x)| <= kAbsLim  <=>  |x| < kAbsLim + 1
         auto stage_batch = [&](int n0, const float2 (&v)[B]) {
             uint32_t amax = 0;  // largest |x| seen, as float bits (NaN / inf sort above all)
-            bool frac = false;
-#pragma unroll
-            for (int r = 0; r < B; ++r) {
-                const int gy = gy0 + n0 + r;
-                const bool ok = col_ok && gy >= rmin && gy < rmax;
-                const float x0 = ok ? v[r].x : 0.0f, x1 = ok ? v[r].y : 0.0f;  // padding is staged as zero (mode="same")
+            unsigned long long frac = 0;  // lanes that saw x != (float)(int)x
+            // one row's two samples: classified, added to the running prefixes; the row's ring entry
+            auto take = [&](float x0, float x1) {
                 const int i0 = (int)x0, i1 = (int)x1;
+#if !WIDE_STAGE_CEILING
                 const uint32_t a0 = __float_as_uint(x0) & 0x7fffffffu, a1 = __float_as_uint(x1) & 0x7fffffffu;
-                frac |= x0 != (float)i0 || x1 != (float)i1;
+                frac |= __builtin_amdgcn_ballot_w64(x0 != (float)i0) | __builtin_amdgcn_ballot_w64(x1 != (float)i1);
                 amax = max(amax, max(a0, a1));
+#endif
                 run0 += (uint32_t)i0;
                 run1 += (uint32_t)i1;
-                int sl = wslot + r;
-                sl = sl >= R ? sl - R : sl;
                 const u32x2w v2 = {run0, run1};
-                *reinterpret_cast<u32x2w*>(Q + sl * G::W + scol) = v2;
-                // the guard copy, in the same batch and so behind the same barrier as its source slot: a chain wave reads
-                // slot R + s only in a window that holds slot s, which the staging then does not write
-                if (sl < C::GR) *reinterpret_cast<u32x2w*>(Q + (sl + R) * G::W + scol) = v2;
+                return v2;
+            };
+            const int g0 = gy0 + n0;
+            if (cols_in && g0 >= rmin && g0 + B <= rmax && wslot + B <= R) {
+                uint32_t* q = Q + wslot * G::W + scol;  // the batch's slots are wslot + r: one address, immediate offsets
+#pragma unroll
+                for (int r = 0; r < B; ++r) {
+                    *reinterpret_cast<u32x2w*>(q + r * G::W) = take(v[r].x, v[r].y);
+                    // (the rows' compare masks are folded as they come, four at a time, not all sixteen rows' at the end: the
+                    // scalar registers they would hold are taken from values that the chain waves' loop then has to reload)
+                    if (r % 4 == 3) asm("" : "+s"(frac));
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < B; ++r) {
+                    const int gy = g0 + r;
+                    const bool ok = col_ok && gy >= rmin && gy < rmax;
+                    int sl = wslot + r;
+                    sl = sl >= R ? sl - R : sl;
+                    // padding is staged as zero (mode="same")
+                    *reinterpret_cast<u32x2w*>(Q + sl * G::W + scol) = take(ok ? v[r].x : 0.0f, ok ? v[r].y : 0.0f);
+                    if (r % 4 == 3) asm("" : "+s"(frac));  // (as on the lean path)
+                }
             }
+            // The guard copies, in the same batch and so behind the same barrier as their source slots: a chain wave reads
+            // slot R + s only in a window that holds slot s, which the staging then does not write.  The batch's slots
+            // below GR are glo .. ghi - 1 - its first ones when it starts there, the ones behind the wrap when it wraps -
+            // and few batches have any: one wave-uniform test a batch, and the lane copies its own entries of those slots
+            // (written above: a wave's LDS operations keep their order) with the slot clamped on the scalar side, so that no
+            // row has a branch of its own.
+            const int glo = wslot < C::GR ? wslot : 0;
+            const int ghi = wslot < C::GR ? C::GR : min(wslot + B - R, C::GR);
+            if (glo < ghi) {
+#pragma unroll
+                for (int g = 0; g < C::GR; ++g) {
+                    const int sl = min(max(g, glo), ghi - 1);
+                    *reinterpret_cast<u32x2w*>(Q + (sl + R) * G::W + scol) = *reinterpret_cast<const u32x2w*>(Q + sl * G::W + scol);
+                }
+            }
+#if WIDE_STAGE_CEILING
+            return 0;
+#else
             // (in a batch without non-finite or absurd samples, x != (float)(int)x is a fractional part)
             const bool wild = __builtin_amdgcn_ballot_w64(amax >= kLimBits) != 0;
-            const bool any_frac = __builtin_amdgcn_ballot_w64(frac) != 0;
+            const bool any_frac = frac != 0;
             const bool bad = wild || any_frac;
             const bool fr = !wild && any_frac;
             return (bad ? kBad : 0) | (fr ? kFracOnly : 0);
+#endif
         };
         auto advance_wslot = [&]() {
             wslot += B;
