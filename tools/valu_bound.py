@@ -13,7 +13,7 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r11_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r12_tpi67_wide_valu_count.json
 
 wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
@@ -52,7 +52,9 @@ def half_rate(op):
             op.startswith("v_mul_lo") or op.startswith("v_mul_hi") or op.startswith("v_lshl_add") or
             op.startswith("v_bfe") or op.startswith("v_perm") or op.startswith("v_cndmask") and op.endswith("e64") or
             op.startswith("v_cmp") or op.startswith("v_max3") or op.startswith("v_min3") or op.startswith("v_readlane") or
-            op.startswith("v_writelane"))
+            op.startswith("v_writelane") or
+            # measured in round 12 (tools/ubench/valu_mix3.hip, profiles/r12_valu_mix3_rate.txt): 1.87 / 1.89 ns at 16 waves per CU
+            op.startswith("v_fract") or op.startswith("v_or3"))
 
 
 WIDE_KERNEL = "tpi_ring_wide_kernelILi67"
@@ -234,6 +236,13 @@ def wide():
             f"lean path: a multiplication per row among the batch's {name}: {muls}"
         assert "v_lshl_add_u64" not in inside, f"lean path: a 64-bit vector address among the batch's {name}"
     assert not any(x.startswith("v_cndmask") for x in lm[first_cvt:last_write + 1]), "lean path: a select among the batch's rows"
+    # the classification (csrc/wide_classify.hpp) converts nothing back and compares nothing per sample: a row is two
+    # v_fract_f32, one OR of three and one v_max3_f32 beside its converts and prefix adds; the batch's compares are on the
+    # two accumulators (round 11 had 32 v_cvt_f32_i32 and 32 v_cmp_neq_f32 here, each compare with a scalar OR behind it)
+    assert not any(x.startswith(("v_cvt_f32_i32", "v_cmp_neq_f32")) for x in lm), "lean path: a convert back or a compare per sample"
+    assert sum(x.startswith("v_cmp") for x in lm) <= 6, "lean path: more compares than a batch's own (flags of two accumulators, lane 0's store)"
+    assert sum(x.startswith("v_fract_f32") for x in lm) == 32 and sum(x.startswith("v_max3_f32") for x in lm) == 16, \
+        "lean path: two v_fract_f32 and one v_max3_f32 a row"
     # The batch's branches, apart from the phase's own.  The staging of a batch comes first in a phase, then lane 0's store
     # of the flags (the one branch on the exec mask), then the next batch's loads, then the barrier; what follows the barrier
     # is the loop's.  In the source a batch makes three choices - lean or general staging, guard copies or none, interior

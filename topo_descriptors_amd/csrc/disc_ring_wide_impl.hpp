@@ -16,7 +16,9 @@
 //   * the staging runs on waves of its own (std_ring_spec_kernel's structure):
 //     waves 0-2 convert, classify and write batch ph + 1 (16 rows, two columns per lane, 8-byte loads) and issue the
 //     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase; a batch whose rows,
-//     columns and slots need no test, clamp or wrap (wave-uniform: nearly all of them) takes a lean path of its own;
+//     columns and slots need no test, clamp or wrap (wave-uniform: nearly all of them) takes a lean path of its own; the
+//     classification is wide_classify.hpp's: per row two fractional parts ORed into one register and one float maximum of
+//     magnitudes into another, three compares a batch;
 //   * prefix sums are uint32 modulo 2^32 with no offset and the finalisation is tpi_march_kernel's expression, so the
 //     bits are those of the marching kernel.
 //
@@ -27,6 +29,8 @@
 // only gets the same bits from every one of them (tpi_scaled_march_kernel), so the granularity of the marking cannot
 // change a bit.  Single-block calls only (no seam parts).
 #pragma once
+
+#include "wide_classify.hpp"
 
 namespace topo {
 
@@ -518,11 +522,11 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         // lane of the wave has its columns in the raster and the batch's slots do not wrap the ring: wave-uniform conditions,
         // one branch a batch, and then no row needs a clamp, a test, a multiplication or a slot wrap of its own.  On the
         // bench DEM that is every batch but a run's first and last ones and the last strip's.
-        // (The lean path leans on three empty asm statements that only hold the optimiser back: the opaque row base and the
-        // statement behind the loads in load_batch, the folding point of the compare masks in stage_batch.  What they buy is
-        // a property of the compiled code, not of the source: after a compiler update run tools/valu_bound.py wide and
-        // tools/spill_survey.py tpi_ring_wide_kernel again - the tool asserts the loads' form, the rows without branch,
-        // select or multiplication, and the size of the chain waves' loop, reloads of spilled registers included.)
+        // (The lean path leans on two empty asm statements in load_batch that only hold the optimiser back: the opaque row
+        // base and the statement behind the loads.  What they buy is a property of the compiled code, not of the source:
+        // after a compiler update run tools/valu_bound.py wide and tools/spill_survey.py tpi_ring_wide_kernel again - the
+        // tool asserts the loads' form, the rows without branch, select, compare, convert back or multiplication, and the
+        // size of the chain waves' loop, reloads of spilled registers included.)
         constexpr bool kLean = WIDE_LEAN || WIDE_STAGE_CEILING;
         const bool cols_in = kLean && __builtin_amdgcn_ballot_w64(col_ok) == ~0ull;
         const uint32_t voff = (uint32_t)(col_ok ? gcol : 0) * 4u;
@@ -559,17 +563,13 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         // (stagers) one batch: convert, classify, prefix, write.  Returns kBad when the batch holds a sample the chain cannot
         // take (fractional, non-finite or absurd) and kFracOnly when it holds fractional samples and no non-finite or absurd
         // one (what the dem_memo report counts, like the marching kernel, which counts no tile it leaves for such samples)
-        const uint32_t kLimBits = __float_as_uint(kAbsLim + 1.0f);  // |trunc(x)| <= kAbsLim  <=>  |x| < kAbsLim + 1
         auto stage_batch = [&](int n0, const float2 (&v)[B]) {
-            uint32_t amax = 0;  // largest |x| seen, as float bits (NaN / inf sort above all)
-            unsigned long long frac = 0;  // lanes that saw x != (float)(int)x
+            WideClassAcc cls;  // the lane's samples of the batch: fractional parts ORed, largest magnitude (wide_classify.hpp)
             // one row's two samples: classified, added to the running prefixes; the row's ring entry
             auto take = [&](float x0, float x1) {
                 const int i0 = (int)x0, i1 = (int)x1;
 #if !WIDE_STAGE_CEILING
-                const uint32_t a0 = __float_as_uint(x0) & 0x7fffffffu, a1 = __float_as_uint(x1) & 0x7fffffffu;
-                frac |= __builtin_amdgcn_ballot_w64(x0 != (float)i0) | __builtin_amdgcn_ballot_w64(x1 != (float)i1);
-                amax = max(amax, max(a0, a1));
+                wide_classify_row(cls, x0, x1);
 #endif
                 run0 += (uint32_t)i0;
                 run1 += (uint32_t)i1;
@@ -580,12 +580,7 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             if (cols_in && g0 >= rmin && g0 + B <= rmax && wslot + B <= R) {
                 uint32_t* q = Q + wslot * G::W + scol;  // the batch's slots are wslot + r: one address, immediate offsets
 #pragma unroll
-                for (int r = 0; r < B; ++r) {
-                    *reinterpret_cast<u32x2w*>(q + r * G::W) = take(v[r].x, v[r].y);
-                    // (the rows' compare masks are folded as they come, four at a time, not all sixteen rows' at the end: the
-                    // scalar registers they would hold are taken from values that the chain waves' loop then has to reload)
-                    if (r % 4 == 3) asm("" : "+s"(frac));
-                }
+                for (int r = 0; r < B; ++r) *reinterpret_cast<u32x2w*>(q + r * G::W) = take(v[r].x, v[r].y);
             } else {
 #pragma unroll
                 for (int r = 0; r < B; ++r) {
@@ -595,7 +590,6 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                     sl = sl >= R ? sl - R : sl;
                     // padding is staged as zero (mode="same")
                     *reinterpret_cast<u32x2w*>(Q + sl * G::W + scol) = take(ok ? v[r].x : 0.0f, ok ? v[r].y : 0.0f);
-                    if (r % 4 == 3) asm("" : "+s"(frac));  // (as on the lean path)
                 }
             }
             // The guard copies, in the same batch and so behind the same barrier as their source slots: a chain wave reads
@@ -616,12 +610,8 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
 #if WIDE_STAGE_CEILING
             return 0;
 #else
-            // (in a batch without non-finite or absurd samples, x != (float)(int)x is a fractional part)
-            const bool wild = __builtin_amdgcn_ballot_w64(amax >= kLimBits) != 0;
-            const bool any_frac = frac != 0;
-            const bool bad = wild || any_frac;
-            const bool fr = !wild && any_frac;
-            return (bad ? kBad : 0) | (fr ? kFracOnly : 0);
+            // |trunc(x)| <= kAbsLim  <=>  |x| < kAbsLim + 1
+            return wide_classify_batch(cls, kAbsLim + 1.0f, kBad, kFracOnly);
 #endif
         };
         auto advance_wslot = [&]() {
