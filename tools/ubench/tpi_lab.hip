@@ -10,7 +10,9 @@
 //     variants any_tpi / any_std / any_tpi_std : the product's dispatch for 67 px, compiled with this build's flags
 //   (-DMARCH_DYN_ROWS=0/1, -DCHAIN_PRIO=0/1, -DMARCH_STAMPS)
 //   -DWIDE_STAMPS=1/2 (variant any_tpi): clock stamps of tpi_ring_wide_kernel<67> at the end of a phase, printed per wave for
-//   two blocks - 1 with the chain waves' output stores drained in front of the barrier, 2 without (the kernel as built)
+//   two blocks - 1 with the chain waves' output stores drained in front of the barrier, 2 without (the kernel as built) - and
+//   per SIMD how much earlier its older chain wave is at the barrier than its younger one; -DWIDE_PRIO=0: no wave touches its
+//   issue priority (the A/B of the priority ladder, profiles/r13_tpi67_prio_stamps.txt)
 //   -DWIDE_STAGE_CEILING=1 (variant any_tpi): tpi_ring_wide_kernel<67> whose staging only converts, prefixes and writes, flags
 //   constant 0 (whole-metre rasters only: the ceiling of a leaner staging stream); -DWIDE_LEAN=0: every batch on the general path
 #include <cstdio>
@@ -122,6 +124,15 @@ int main(int argc, char** argv) {
                        k ? "mid" : "  0", w, w < 3 ? "stager" : "chain ", s[0], s[1] / n, s[2] / n, s[3] / n, s[4] / n,
                        s[1] ? 100.0 * ((double)s[2] - (double)s[4]) / (double)s[1] : 0.0);
             }
+        // wave w runs on SIMD w mod 4: per SIMD how much longer its older chain wave waits at the barrier than its younger one
+        for (int k = 0; k < topo::kWideStampBlocks; ++k) {
+            printf("blk %s older chain wave at the barrier before the younger, SIMD 0 .. 3:", k ? "mid" : "  0");
+            for (int simd = 0; simd < 4; ++simd) {
+                const unsigned long long *a = st[k][simd == 3 ? 3 : 4 + simd], *b = st[k][simd == 3 ? 7 : 8 + simd];
+                printf(" %.0f", (double)a[3] / (a[0] ? (double)a[0] : 1.0) - (double)b[3] / (b[0] ? (double)b[0] : 1.0));
+            }
+            printf(" ticks\n");
+        }
     }
 #endif
     unsigned long long* d_bad = nullptr;

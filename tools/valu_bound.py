@@ -13,7 +13,7 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r12_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r13_tpi67_wide_valu_count.json
 
 wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
 row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
@@ -22,7 +22,9 @@ row loop per VALID output column: offline, before any GPU time.  A chain wave su
 sweep, the finalisation and the stores of both rows, the barrier - and an output row is half of it.  Vector adds whose
 result is a ds_read address are counted as their own class.  The staging waves' phase loop is reported beside it
 (staging_phase_loop): every instruction the loop holds, and the way round it that an interior batch takes (the lean path of
-stage_batch and load_batch) - instructions, VALU by opcode, scalar instructions, branches, the VALU's price.
+stage_batch and load_batch) - instructions, VALU by opcode, scalar instructions, branches, the VALU's price.  The issue
+priorities (WIDE_PRIO) are part of the count: the chain loop's s_setprio levels and the VALU each covers, the staging
+loop's raise and drop (priority_ladder, priority), with the ladder's shape asserted.
 
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
@@ -190,14 +192,54 @@ def staging_report(lines):
             "valu_ns": round(ns, 1)}
 
 
-def wide():
+def wide_asm(extra=()):
+    """The ISA of a device-only compile of the wide kernel from the product's header (`extra`: further compiler flags)."""
     csrc = os.path.join(REPO, "topo_descriptors_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         src, asm = os.path.join(tmp, "wide.hip"), os.path.join(tmp, "wide.s")
         open(src, "w").write(WIDE_SRC)
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        "-I", csrc, "-I", os.path.join(REPO, "include"), src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
-        txt = open(asm).read()
+                        "-I", csrc, "-I", os.path.join(REPO, "include"), *extra, src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
+        return open(asm).read()
+
+
+def chain_phase_loop(txt):
+    """The chain waves' phase loop: ONE sweep over the wave's row pair (55 distinct prefix rows of the pair's 84, three
+    ds_read_b64 each), the float64 finalisation and the stores of both rows, the barrier."""
+    return loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 3 * 42 and any("f64" in x for x in o))
+
+
+# The chain waves' priority ladder (WIDE_PRIO): the wave behind catches up while the wave ahead sits a level lower, so the
+# lag between a SIMD's two chain waves is bounded by a level's width - no level may hold more than LEVEL_SHARE of the loop's
+# VALU - and on the last level, where both are at 0 and age alone decides, the younger wave runs on alone once the older is
+# through: at most LAST_SHARE.
+LEVEL_SHARE, LAST_SHARE = 0.40, 0.20
+
+
+def ladder_report(ph):
+    """The s_setprio levels of the chain waves' phase loop and the VALU each covers (asserts the ladder's shape)."""
+    at = [(i, int(x.split()[1])) for i, x in enumerate(ph) if x.startswith("s_setprio")]
+    levels = [l for _, l in at]
+    assert levels == sorted(set(levels), reverse=True) and len(levels) >= 2 and levels[0] == 3, f"chain loop: the levels {levels} do not descend from 3"
+    # (the output stores: the loop's layout puts the phase's bookkeeping, the tile map's stores among it, in front of the sweep)
+    stores = [i for i, x in enumerate(ph) if x.startswith("global_store_dwordx2") and i > at[0][0]]
+    assert levels[-1] == 0 and stores and at[-1][0] < stores[0], "chain loop: the wave is not back at 0 before its first output store"
+    assert not any(x.startswith(("s_cbranch", "s_branch")) for x in ph[at[0][0]:at[-1][0]]), "chain loop: a branch inside the sweep"
+    ends = [i for i, _ in at[1:]] + [len(ph)]
+    segs = [[x.split()[0] for x in ph[a:b] if x.startswith("v_")] for (a, _), b in zip(at, ends)]
+    valu = [len(v) for v in segs]
+    total = sum(x.startswith("v_") for x in ph)
+    shares = [round(v / total, 3) for v in valu]
+    assert max(shares) <= LEVEL_SHARE, f"chain loop: a level holds {max(shares)} of the VALU (at most {LEVEL_SHARE})"
+    assert shares[-1] <= LAST_SHARE, f"chain loop: the last level holds {shares[-1]} of the VALU (at most {LAST_SHARE})"
+    return {"levels": levels, "valu_by_level": valu, "ns_by_level": [round(price(v)[2], 1) for v in segs], "share_by_level": shares,
+            "valu_outside_the_ladder": total - sum(valu), "bounds": {"level_share": LEVEL_SHARE, "last_level_share": LAST_SHARE},
+            "last_level_before_first_store": True}
+
+
+def wide():
+    txt = wide_asm()
+    with tempfile.TemporaryDirectory() as tmp:
         lab = os.path.join(tmp, "lab.s")
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S",
                         "--cuda-device-only", os.path.join(REPO, "tools", "ubench", "tpi_lab.hip"), "-o", lab],
@@ -205,10 +247,11 @@ def wide():
         txt_m = open(lab).read()
     # the chain waves' phase loop: ONE sweep over the wave's row pair (55 distinct prefix rows of the pair's 84, three
     # ds_read_b64 each), the float64 finalisation and the stores of both rows, the barrier; an output row is half of it
-    ph = loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 3 * 42 and any("f64" in x for x in o))
+    ph = chain_phase_loop(txt)
     mn = [x.split()[0] for x in ph]
     assert mn.count("ds_read_b64") == 3 * 55, "a row pair: 55 prefix rows of three reads"
-    assert mn.count("s_setprio") in (0, 4), "no priority ladder, or the sweep's 3, 2, 1, 0 (WIDE_PRIO)"
+    # the issue-priority ladder (WIDE_PRIO): 3, 2, 1, 0 over the sweep, back at 0 before the finalisation's stores
+    ladder = ladder_report(ph)
     # a chain wave has no load in flight, only its output stores: a vmcnt wait in its phase loop can only wait for those
     # (round 10: the staging waves' last loads, open where the two paths meet, put four such waits there)
     vm_waits = [i for i, x in enumerate(ph) if x.startswith("s_waitcnt") and "vmcnt" in x]
@@ -249,6 +292,11 @@ def wide():
     # rows or not for the loads - and the compiler lays each two-sided choice out as the general block under one branch and
     # the lean block under a second one on a flag the first side sets: 2 + 1 branches for the staging, 2 for the loads.
     # (One branch per choice, two or three a batch, is what the source asks for; the second branch of a pair is the compiler's.)
+    # the staging waves stand on top of the ladder while they stage: up before the batch's first convert, down again behind
+    # its last ring write and before the wave waits at the barrier
+    sp = [(i, int(x.split()[1])) for i, x in enumerate(st_lean) if x.startswith("s_setprio")]
+    assert [l for _, l in sp] == [3, 0], f"lean path: the staging waves' priority goes {[l for _, l in sp]}, not 3 then 0"
+    assert sp[0][0] < first_cvt and last_write < sp[1][0] < lm.index("s_barrier"), "lean path: raised before the first convert, lowered before the barrier"
     cond = [i for i, x in enumerate(lm) if x.startswith("s_cbranch")]
     flag_store = [i for i in cond if lm[i] == "s_cbranch_execz"]
     assert len(flag_store) == 1 and "s_barrier" in lm, "lean path: lane 0's flag store and the phase barrier mark the batch's parts"
@@ -266,7 +314,8 @@ def wide():
     kinds["ds_read_address"] = n_addr
     pair = {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b64": o.count("ds_read_b64"), "s_nop": o.count("s_nop"),
             "salu": sum(1 for x in o if x.startswith("s_")), "global_store_dwordx2": o.count("global_store_dwordx2"),
-            "vmcnt_waits": len(vm_waits), "sgpr_reloads": reloads, "instructions": len(o), "ns": round(ns, 1)}
+            "vmcnt_waits": len(vm_waits), "sgpr_reloads": reloads, "instructions": len(o), "ns": round(ns, 1),
+            "priority_ladder": ladder}
     # per output row: half the pair
     valu = valu[:len(valu) // 2]
     kinds = Counter({k: v / 2 for k, v in kinds.items()})
@@ -276,7 +325,9 @@ def wide():
         "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns): half the row pair of the phase loop",
         "row_pair_instructions": pair,
         "staging_phase_loop": {"whole_loop": staging_report(st_all),
-                               "lean_path": dict(staging_report(st_lean), batch_branches={"staging": stage_branches, "loads": load_branches})},
+                               "lean_path": dict(staging_report(st_lean), batch_branches={"staging": stage_branches, "loads": load_branches},
+                                                 priority={"levels": [l for _, l in sp], "raised_before_first_convert": True,
+                                                           "lowered_before_barrier": True})},
         "row_loop_instructions": {"valu": pair["valu"] / 2, "by_kind": dict(kinds), "ds_read_b128": o.count("ds_read_b128") / 2,
                                   "ds_read_b64": o.count("ds_read_b64") / 2, "v_mov_b32_dpp": o.count("v_mov_b32_dpp") / 2,
                                   "s_nop": o.count("s_nop") / 2, "salu": sum(1 for x in o if x.startswith("s_")) / 2},

@@ -293,9 +293,10 @@ struct WSweep {
 #ifndef WIDE_LEAD
 #define WIDE_LEAD 2
 #endif
-// (lab switch: 1 runs the sweep under the issue-priority ladder of wide_pair_sum; measured slower than without, see there)
+// (1: the issue-priority ladder of wide_pair_sum for the chain waves, and the staging waves at priority 3 while they stage
+// a batch; 0: no wave touches its priority, the kernel of rounds 9 - 12, kept as the A/B switch.  See wide_pair_sum.)
 #ifndef WIDE_PRIO
-#define WIDE_PRIO 0
+#define WIDE_PRIO 1
 #endif
 
 // (lab switch: 1 stamps the clock around what a wave waits for at the end of a phase - a drain of the chain waves' output
@@ -336,13 +337,19 @@ typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 // DL <= lane < 64 - DL), ctr[w][t] that pixel's own value.  The runs go in the order WGeo::S.order; fetch i loads the
 // prefix rows of the pair that no earlier fetch has loaded (WPair), and both rows' differences of a run are formed from
 // the loaded rows, the shared ones among them.
-// PRIO (WIDE_PRIO, off): the wave's issue priority goes 3 -> 2 -> 1 -> 0 over the sweep's steps (CHAIN_PRIO,
+// PRIO (WIDE_PRIO, on): the wave's issue priority goes 3 -> 2 -> 1 -> 0 over the sweep's steps (CHAIN_PRIO,
 // disc_wave_impl.hpp), the counterpart of the 3 -> 2, 1 -> 0 pair that made the two chain waves of a SIMD advance together
-// when each summed its two rows one after the other.  With ONE sweep per wave and phase it loses: a bench step took
-// 4.12 - 4.13 ms with the ladder where the two-sweep kernel took 3.66 - 3.69 ms, and without it 3.38 ms against 3.50 ms
-//  - the chain waves then outrank the staging waves for most of a phase, and the barrier waits for
-// those.  A compile-time choice, and no branch in the sweep either
-// way: a DPP move and the add it feeds fold into one DPP add only within a basic block.
+// when each summed its two rows one after the other.  A SIMD serves the higher priority first and among equals the older
+// wave, so without a ladder the older chain wave of a SIMD runs nearly unimpeded, reaches the barrier some 2300 ticks of a
+// phase's 8800 before the younger, and the younger runs that quarter of a phase alone, at half the rate a SIMD can issue.  With the
+// ladder the wave behind always outranks or ties the wave ahead and the two leapfrog a level at a time: the gap is about 440
+// ticks and a phase about 8160.  The ladder holds only with the staging waves on top of it: they raise themselves to 3
+// while they stage a batch (run_phases) and drop to 0 for the next batch's loads and the barrier, and being the oldest waves
+// they win the tie with a chain wave at 3.  The ladder alone (round 9) lost, 4.12 against 3.68 ms a bench step: chain waves
+// at 3, 2 and 1 hold a staging wave at 0 back by thousands of ticks (rounds 9 and 13).  The
+// wave leaves the sweep at 0 - the finalisation and the stores run there - and a wave that sweeps nothing in a phase never
+// raised itself.  A compile-time choice, and no branch in the sweep either way: a DPP move and the add it feeds fold into
+// one DPP add only within a basic block.
 template <int SIZE, int R, int GR, int LEAD, bool PRIO>
 __device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[2][NCW], uint32_t (&ctr)[2][NCW]) {
     using G = WGeo<SIZE>;
@@ -682,8 +689,13 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             }
             if constexpr (stg) {
                 // the batch phase ph + 1 needs, into the slots behind this phase's window; then the loads of the one after
+                // (WIDE_PRIO: on top of the chain waves' ladder from the barrier until the flags are written, then back to 0
+                // for the loads and the wait at the barrier.  s_setprio ignores EXEC: both stand on this wave-uniform path,
+                // outside lane 0's store)
+                if constexpr (WIDE_PRIO != 0) CHAIN_SETPRIO(3);
                 const int seen = stage_batch(C::PRO + ph * B, va);
                 if (lane == 0) wflags[((ph + 1) & 1) * SW + wave] = seen;
+                if constexpr (WIDE_PRIO != 0) CHAIN_SETPRIO(0);
                 load_batch(C::PRO + (ph + 1) * B, va);
             } else if (compute) {
                 static_assert(C::RPW == 2, "a chain wave sums its two rows of a phase in one sweep");
