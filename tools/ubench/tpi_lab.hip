@@ -12,7 +12,9 @@
 //   -DWIDE_STAMPS=1/2 (variant any_tpi): clock stamps of tpi_ring_wide_kernel<67> at the end of a phase, printed per wave for
 //   two blocks - 1 with the chain waves' output stores drained in front of the barrier, 2 without (the kernel as built) - and
 //   per SIMD how much earlier its older chain wave is at the barrier than its younger one; -DWIDE_PRIO=0: no wave touches its
-//   issue priority (the A/B of the priority ladder, profiles/r13_tpi67_prio_stamps.txt)
+//   issue priority (the A/B of the priority ladder, profiles/r13_tpi67_prio_stamps.txt); -DWIDE_BOUNDARY=1: the chain waves'
+//   lead fetches in front of the phase barrier, their phase state by increments (round 14: measured, not kept) - the stamps
+//   also give a chain wave's ticks from the barrier to the arrival of its lead rows (profiles/r14_tpi67_boundary_stamps.txt)
 //   -DWIDE_STAGE_CEILING=1 (variant any_tpi): tpi_ring_wide_kernel<67> whose staging only converts, prefixes and writes, flags
 //   constant 0 (whole-metre rasters only: the ceiling of a leaner staging stream); -DWIDE_LEAN=0: every batch on the general path
 #include <cstdio>
@@ -115,6 +117,7 @@ int main(int argc, char** argv) {
         // of its phases, of the chain waves' store drain in front of the phase barrier, of the barrier, of a stamp pair
         unsigned long long st[topo::kWideStampBlocks][topo::kWideStampWaves][topo::kWideStampFields];
         if (hipMemcpyFromSymbol(st, HIP_SYMBOL(topo::wide_stamps), sizeof(st)) != hipSuccess) return 1;
+        printf("WIDE_BOUNDARY %d, %d valid columns a strip\n", WIDE_BOUNDARY, topo::WGeo<SIZE>::TILE_W);
         for (int k = 0; k < topo::kWideStampBlocks; ++k)
             for (int w = 0; w < topo::kWideStampWaves; ++w) {
                 const unsigned long long* s = st[k][w];
@@ -123,6 +126,13 @@ int main(int argc, char** argv) {
                        "   drain less the pair: %.2f %% of a phase\n",
                        k ? "mid" : "  0", w, w < 3 ? "stager" : "chain ", s[0], s[1] / n, s[2] / n, s[3] / n, s[4] / n,
                        s[1] ? 100.0 * ((double)s[2] - (double)s[4]) / (double)s[1] : 0.0);
+                // a chain wave's way from the barrier to its sweep: the stamp behind the barrier to the stamp where the lead
+                // rows have arrived (both stamps wait for the wave's LDS reads; a stamp pair's own ticks are beside it)
+                if (w >= 3 && s[5])
+                    printf("                      sweeps behind a barrier %llu  barrier to lead rows %.1f ticks, less the pair %.1f:"
+                           " %.2f %% of a phase\n",
+                           s[5], (double)s[6] / (double)s[5], (double)s[6] / (double)s[5] - s[4] / n,
+                           s[1] ? 100.0 * ((double)s[6] / (double)s[5] - s[4] / n) / (s[1] / n) : 0.0);
             }
         // wave w runs on SIMD w mod 4: per SIMD how much longer its older chain wave waits at the barrier than its younger one
         for (int k = 0; k < topo::kWideStampBlocks; ++k) {

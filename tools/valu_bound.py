@@ -13,10 +13,10 @@ SQ_INSTS_VALU counter minus the row loop's share and are priced at the kernel's 
     python tools/valu_bound.py [SQ_INSTS_VALU per launch, default from profiles/r06_tpi67_pmc_summary.txt] > profiles/r06_tpi67_valu_bound.json
     python tools/valu_bound.py std [SQ_INSTS_VALU per launch, default from profiles/r06_std67_pmc_summary.txt] > profiles/r06_std67_valu_bound.json
 
-    python tools/valu_bound.py wide > profiles/r13_tpi67_wide_valu_count.json
+    python tools/valu_bound.py wide > profiles/r14_tpi67_wide_valu_count.json
 
-wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 312 valid columns a
-row) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
+wide: one output row of tpi_ring_wide_kernel<67> (csrc/disc_ring_wide_impl.hpp: 6 columns per lane, 316 valid columns a
+row, the number read from the compiled unit) counted the same way from a device-only compile of the product's header, and set against the marching kernel's
 row loop per VALID output column: offline, before any GPU time.  A chain wave sums its two rows of a phase in one sweep
 (55 distinct prefix rows of three ds_read_b64 for the pair), so the count is that of the chain waves' phase loop - the
 sweep, the finalisation and the stores of both rows, the barrier - and an output row is half of it.  Vector adds whose
@@ -24,7 +24,9 @@ result is a ds_read address are counted as their own class.  The staging waves' 
 (staging_phase_loop): every instruction the loop holds, and the way round it that an interior batch takes (the lean path of
 stage_batch and load_batch) - instructions, VALU by opcode, scalar instructions, branches, the VALU's price.  The issue
 priorities (WIDE_PRIO) are part of the count: the chain loop's s_setprio levels and the VALU each covers, the staging
-loop's raise and drop (priority_ladder, priority), with the ladder's shape asserted.
+loop's raise and drop (priority_ladder, priority), with the ladder's shape asserted.  The chain waves' way from the phase
+barrier to the sweep's first subtract is walked and counted (phase_boundary), for the loop that ships and for the lab switch
+-DWIDE_BOUNDARY=1 (round 14: the next phase's lead fetches in front of the barrier; measured, not kept), whose shape is asserted.
 
 std (round 4): the same for std_ring_kernel<67, false> - its phase loop (one output row of 256 pixels per wave and
 phase: two chains, the staging share of the wave, the finalisation) priced by issue class; the scalar instructions of
@@ -61,7 +63,9 @@ def half_rate(op):
 
 WIDE_KERNEL = "tpi_ring_wide_kernelILi67"
 WIDE_SRC = """#include "disc_wave_impl.hpp"
-namespace topo { int wide_probe(const Block& b, float* t) { return launch_ring_wide<67>(b, t, 60, 184); } }
+namespace topo { int wide_probe(const Block& b, float* t) { return launch_ring_wide<67>(b, t, 60, 184); }
+extern "C" __device__ __attribute__((used)) const int wide_probe_tile_w = WGeo<67>::TILE_W;
+extern "C" __device__ __attribute__((used)) const int wide_probe_lead_rows = WPair<67, WideCfg<67>::GR>::lead_rows(WIDE_LEAD); }
 """
 
 
@@ -209,6 +213,109 @@ def chain_phase_loop(txt):
     return loop_lines(txt, WIDE_KERNEL, lambda o: sum(x == "ds_read_b64" for x in o) >= 3 * 42 and any("f64" in x for x in o))
 
 
+def probe_constant(txt, name):
+    """A constant of the compiled unit (WIDE_SRC): what the headers themselves say."""
+    return int(re.search(r"^%s:\s*\n\s*\.long\s+(\d+)" % name, txt, re.M).group(1))
+
+
+def chain_loop_blocks(txt):
+    """The chain waves' phase loop (chain_phase_loop) as basic blocks, labels kept: [label or None, [instructions]]."""
+    start = txt.index(WIDE_KERNEL + SUFFIX)
+    lines = txt[start:txt.index("s_endpgm", start)].split("\n")
+    labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
+    best = None
+    for i, l in enumerate(lines):
+        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.search(r"s_branch\s+(\.LBB\d+_\d+)", l)
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            body = lines[labels[m.group(1)]:i + 1]
+            mn = [x.split()[0] for x in body if x.strip() and not x.strip().startswith((".", ";", "//")) and not x.strip().endswith(":")]
+            if sum(x == "ds_read_b64" for x in mn) >= 3 * 42 and any("f64" in x for x in mn) and (best is None or i - labels[m.group(1)] < best[1] - best[0]):
+                best = (labels[m.group(1)], i)
+    assert best is not None, "no chain phase loop found"
+    # (the loop's layout may put blocks of it in front of the label its last branch returns to: taken in with the body)
+    a, b = best
+    while True:
+        tg = [labels[t] for l in lines[a:b + 1] for t in re.findall(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l) if t in labels and labels[t] < a]
+        if not tg:
+            break
+        a = min(tg)
+    return blocks_of(lines[a:b + 1])
+
+
+def boundary_path(bl):
+    """The hot path of a chain wave from the phase barrier to the sweep: the way through the loop's blocks (the back edge
+    included) with the fewest instructions from behind s_barrier to the first vector subtract behind `s_setprio 3`.
+    Returns the instructions on it, the barrier and the subtract excluded."""
+    at = {b[0]: k for k, b in enumerate(bl) if b[0]}
+    bar = [(k, i) for k, b in enumerate(bl) for i, x in enumerate(b[1]) if x.startswith("s_barrier")]
+    assert len(bar) == 1, f"chain loop: {len(bar)} barriers"
+
+    def sweep_start(ins, lo=0):
+        """Index of the first v_sub_u32 behind an `s_setprio 3` among ins[lo:], or None."""
+        raised = False
+        for i in range(lo, len(ins)):
+            raised = raised or ins[i].split()[:2] == ["s_setprio", "3"]
+            if raised and ins[i].startswith("v_sub_u32"):
+                return i
+        return None
+
+    def succ(k):
+        last = bl[k][1][-1] if bl[k][1] else ""
+        out = []
+        if last.startswith(("s_cbranch", "s_branch")):
+            tgt = last.split()[1]
+            if tgt in at:
+                out.append(at[tgt])
+        if not last.startswith("s_branch") and k + 1 < len(bl):
+            out.append(k + 1)
+        return out
+
+    k0, i0 = bar[0]
+    end = sweep_start(bl[k0][1], i0 + 1)
+    if end is not None:
+        return bl[k0][1][i0 + 1:end]
+    # Dijkstra over the blocks: cost = instructions issued
+    import heapq
+    heap = [(len(bl[k0][1]) - i0 - 1, n, bl[k0][1][i0 + 1:]) for n in succ(k0)]
+    heapq.heapify(heap)
+    done = set()
+    while heap:
+        cost, k, path = heapq.heappop(heap)
+        if k in done:
+            continue
+        done.add(k)
+        end = sweep_start(bl[k][1])
+        if end is not None:
+            return path + bl[k][1][:end]
+        for n in succ(k):
+            if n not in done:
+                heapq.heappush(heap, (cost + len(bl[k][1]), n, path + bl[k][1]))
+    raise AssertionError("chain loop: no way from the barrier to the sweep")
+
+
+def boundary_report(txt, lead_rows):
+    """The chain waves' phase boundary (WIDE_BOUNDARY): the lead fetches in front of the barrier, the hot path behind it."""
+    bl = chain_loop_blocks(txt)
+    ph = [x for b in bl for x in b[1]]
+    prio = [i for i, x in enumerate(ph) if x.startswith("s_setprio")]
+    stores = [i for i, x in enumerate(ph) if x.startswith("global_store_dwordx2") and i > prio[0]]
+    bar = [i for i, x in enumerate(ph) if x.startswith("s_barrier")][0]
+    # (in the loop's order: what follows the last output store, round the back edge if the barrier stands in front of it)
+    between = ph[stores[-1] + 1:bar] if bar > stores[-1] else ph[stores[-1] + 1:] + ph[:bar]
+    reads = [i for i, x in enumerate(between) if x.startswith("ds_read_b64")]
+    wait0 = bool(reads) and any(x.startswith("s_waitcnt") and "lgkmcnt(0)" in x for x in between[reads[0]:])
+    path = boundary_path(bl)
+    mn = [x.split()[0] for x in path]
+    to_prio = mn[:max(i for i, x in enumerate(path) if x.split()[:2] == ["s_setprio", "3"])] if "s_setprio" in mn else mn
+    return {"lead_rows": lead_rows, "lead_reads_between_last_store_and_barrier": len(reads),
+            "lgkmcnt0_wait_between_lead_reads_and_barrier": wait0,
+            "hot_path_barrier_to_first_subtract": len(path),
+            "hot_path_salu": sum(x.startswith("s_") for x in mn), "hot_path_valu": sum(x.startswith("v_") for x in mn),
+            "hot_path_ds_reads": sum(x.startswith("ds_read") for x in mn),
+            "hot_path_waits": [x for x in path if x.startswith("s_waitcnt")],
+            "multiplies_and_readlanes_before_the_sweep": [x for x in to_prio if x.startswith(("s_mul_hi", "s_mulk_i32", "v_readlane"))]}
+
+
 # The chain waves' priority ladder (WIDE_PRIO): the wave behind catches up while the wave ahead sits a level lower, so the
 # lag between a SIMD's two chain waves is bounded by a level's width - no level may hold more than LEVEL_SHARE of the loop's
 # VALU - and on the last level, where both are at 0 and age alone decides, the younger wave runs on alone once the older is
@@ -260,6 +367,27 @@ def wide():
     # path's pressure pushes into a VGPR lane comes back here as a v_readlane, which is VALU and is reported beside the count)
     reloads = sum(x.startswith(("v_readlane", "v_writelane")) for x in mn)
     assert sum(x.startswith("v_") for x in mn) <= 812, f"the chain waves' phase loop grew ({reloads} reloads of spilled scalar registers in it)"
+    # The phase boundary.  What ships is round 13's: slot, rows and lead fetches formed behind the barrier.  The lab switch
+    # -DWIDE_BOUNDARY=1 (round 14: measured, not kept) is compiled and walked beside it so that it stays what was measured:
+    # the lead fetches of the NEXT phase between the last output store and the barrier with no wait for them in front of it,
+    # no multiplication and no reload of a spilled scalar on the hot path from the barrier to the sweep, and that path
+    # shorter than the shipped one.
+    lead_rows = probe_constant(txt, "wide_probe_lead_rows")
+    boundary = boundary_report(txt, lead_rows)
+    assert boundary["lead_reads_between_last_store_and_barrier"] == 0, "the shipped loop fetches in front of the barrier"
+    lab_txt = wide_asm(["-DWIDE_BOUNDARY=1"])
+    lab_mn = [x.split()[0] for x in chain_phase_loop(lab_txt)]
+    lab = boundary_report(lab_txt, lead_rows)
+    lab.update({"valu": sum(x.startswith("v_") for x in lab_mn), "ds_read_b64": lab_mn.count("ds_read_b64"),
+                "salu": sum(x.startswith("s_") for x in lab_mn), "instructions": len(lab_mn)})
+    assert lab["lead_reads_between_last_store_and_barrier"] == 3 * lead_rows, \
+        f"WIDE_BOUNDARY=1: {lab['lead_reads_between_last_store_and_barrier']} reads between the last store and the barrier, not {3 * lead_rows}"
+    assert not lab["lgkmcnt0_wait_between_lead_reads_and_barrier"], "WIDE_BOUNDARY=1: the lead fetches are waited for in front of the barrier"
+    assert not lab["multiplies_and_readlanes_before_the_sweep"], \
+        f"WIDE_BOUNDARY=1: behind the barrier, before the sweep: {lab['multiplies_and_readlanes_before_the_sweep']}"
+    assert lab["hot_path_barrier_to_first_subtract"] < boundary["hot_path_barrier_to_first_subtract"], \
+        "WIDE_BOUNDARY=1: the way from the barrier to the sweep is no shorter than the shipped one"
+    boundary["lab_WIDE_BOUNDARY_1"] = lab
     row = ph
     o = mn
     # the staging waves' phase loop, and within it the lean path of an interior batch: its rows - from the first load to the
@@ -315,14 +443,16 @@ def wide():
     pair = {"valu": len(valu), "by_kind": dict(kinds), "ds_read_b64": o.count("ds_read_b64"), "s_nop": o.count("s_nop"),
             "salu": sum(1 for x in o if x.startswith("s_")), "global_store_dwordx2": o.count("global_store_dwordx2"),
             "vmcnt_waits": len(vm_waits), "sgpr_reloads": reloads, "instructions": len(o), "ns": round(ns, 1),
-            "priority_ladder": ladder}
+            "priority_ladder": ladder, "phase_boundary": boundary}
     # per output row: half the pair
     valu = valu[:len(valu) // 2]
     kinds = Counter({k: v / 2 for k, v in kinds.items()})
     ns /= 2
-    cols, cols_m = 312, TILE_W
+    # the strip's valid columns: WGeo<67>::TILE_W, read from the compiled unit's own constant
+    cols, cols_m = probe_constant(txt, "wide_probe_tile_w"), TILE_W
+    assert cols == 316, f"a strip's valid columns: {cols}, not 316"
     print(json.dumps({
-        "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (52 lanes x 6 columns): half the row pair of the phase loop",
+        "kernel": "tpi_ring_wide_kernel<67>, one chain-wave row (316 columns: 52 lanes x 6 and a pair either side): half the row pair of the phase loop",
         "row_pair_instructions": pair,
         "staging_phase_loop": {"whole_loop": staging_report(st_all),
                                "lean_path": dict(staging_report(st_lean), batch_branches={"staging": stage_branches, "loads": load_branches},

@@ -4,8 +4,9 @@
 // 18 run-in lanes of a 4-column layout waste 28 % (46 of 64 lanes write a sum) and the lane hops - 17 DPP forms per
 // output column, every one at half rate - a further fifth (profiles/r06_tpi67_valu_bound.json).  Here:
 //
-//   * a lane owns NCW = 6 adjacent columns: 6 lane hops per side for 67 px, 52 of 64 lanes valid (312 of 384 staged
-//     columns), the chain two-sided and rim first as in ring_disc_sum (disc_ring_impl.hpp);
+//   * a lane owns NCW = 6 adjacent columns: 6 lane hops per side for 67 px, 52 of 64 lanes valid in all their columns and
+//     the lane either side of them in one pair (316 of 384 staged columns: the disc reaches 33 columns, not 36; WGeo::XV),
+//     the chain two-sided and rim first as in ring_disc_sum (disc_ring_impl.hpp);
 //   * a ring row is 384 dwords (1.5 KiB), staged column c at dword c: lane l reads its 6 columns as three ds_read_b64 at
 //     +0, +8 and +16 from byte 24 l (dwords 6 l, 6 l + 1 of the 32 lanes of a group are distinct mod 64: conflict-free);
 //   * the ring holds R = SIZE + 32 rows plus GR = 6 guard rows behind them, copies of slots 0 .. GR - 1 (WideCfg), so
@@ -15,7 +16,8 @@
 //     67 px where two single rows read 84, and each is read once;
 //   * the staging runs on waves of its own (std_ring_spec_kernel's structure):
 //     waves 0-2 convert, classify and write batch ph + 1 (16 rows, two columns per lane, 8-byte loads) and issue the
-//     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase; a batch whose rows,
+//     loads of batch ph + 2 while waves 3-10 run two output rows each of phase ph; ONE barrier per phase, in front of which
+//     a chain wave has already issued the first fetches of its next sweep (WIDE_BOUNDARY); a batch whose rows,
 //     columns and slots need no test, clamp or wrap (wave-uniform: nearly all of them) takes a lean path of its own; the
 //     classification is wide_classify.hpp's: per row two fractional parts ORed into one register and one float maximum of
 //     magnitudes into another, three compares a batch;
@@ -44,10 +46,14 @@ struct WGeo {
     static_assert(T.centre == 0 && T.off_min == -T.off_max, "odd disc sizes only");
     static constexpr int M = T.off_max;
     static constexpr int DL = (M + NCW - 1) / NCW;  // lane hops per side
-    static constexpr int NVL = 64 - 2 * DL;         // lanes that end up with full sums
-    static constexpr int TILE_W = NCW * NVL;        // valid output columns per strip
-    static constexpr int X0 = NCW * DL;             // staged column of the first valid output
+    static constexpr int NVL = 64 - 2 * DL;         // lanes that end up with full sums in all their columns
     static constexpr int W = 64 * NCW;              // staged columns = dwords per ring row
+    // The disc needs M staged columns a side, not NCW DL: the lanes next to the whole ones (DL - 1 and 64 - DL) hold valid
+    // sums in the columns whose step DL takes nothing (WSweep::edges_valid), and the hops shift zeros in at the wave's ends.
+    // Stores go by pairs of columns, so the first valid staged column is M rounded up to even.
+    static constexpr int XV = (M + 1) / 2 * 2;      // first staged column that is stored
+    static constexpr int TILE_W = W - 2 * XV;       // valid output columns per strip
+    static constexpr int X0 = XV;                   // staged column of the first valid output
     static constexpr int NR = T.num_runs;
     static_assert(NVL >= 16, "disc too wide for one wavefront");
     // RGeo::Sched for 6 columns per lane: per run the largest step that uses it, the runs in the order first needed
@@ -185,6 +191,29 @@ struct WPair {
         }
         return true;
     }
+    // the rows the first `lead` fetches load, and the largest Q index among them
+    static constexpr int lead_rows(int lead) {
+        int n = 0;
+        for (int i = 0; i < lead && i < NR; ++i) n += T.nload[i];
+        return n;
+    }
+    static constexpr int lead_bases(int lead) {
+        int n = 0;
+        for (int b = 0; b < T.nb; ++b) n += T.first[b] < lead ? 1 : 0;
+        return n;
+    }
+    static constexpr int lead_reach(int lead) {
+        int m = 0;
+        for (int i = 0; i < lead && i < NR; ++i)
+            for (int n = 0; n < T.nload[i]; ++n) m = T.load[i][n] > m ? T.load[i][n] : m;
+        return m;
+    }
+    // The lead fetches of a pair's NEXT phase may be issued in front of the barrier that ends this one: in indices
+    // u = j + k of the next phase's window (j: the pair's first row in the phase, at most B - 2; k: the Q index) the batch
+    // that barrier publishes is u = 2 M + 1 .. 2 M + B, everything below it was published a barrier earlier, and the staging
+    // waves meanwhile write only slots of rows older than the window.  So: the lead fetches' largest k plus B - 2 is at most 2 M.
+    template <int LEAD, int B>
+    static constexpr bool lead_is_published() { return lead_reach(LEAD) + B - 2 <= 2 * G::M; }
     // the rows a pair would read without sharing (four a run), and what the run heights of the disc leave of them
     static constexpr int kUnshared = 4 * NR;
     static_assert(check(), "every row loaded once, before its uses, within GR rows of a base formed by then");
@@ -283,7 +312,23 @@ struct WSweep {
                 }
         return true;
     }
+    // every stored column (staged XV .. W - XV - 1) has its taps among the staged columns, and where a step's source lane
+    // lies beyond the wave's ends (-1, 64: the hop shifts a zero in) that step takes nothing for the column
+    static constexpr bool edges_valid() {
+        for (int c = G::XV; c < G::W - G::XV; ++c) {
+            const int lane = c / NCW, o = c % NCW;
+            if (c - G::M < 0 || c + G::M > G::W - 1) return false;
+            for (int D = 0; D <= G::DL; ++D) {
+                if (lane + D > 63 && T.firstR[D][o] >= 0) return false;
+                if (lane - D < 0 && T.firstL[D][o] >= 0) return false;
+            }
+        }
+        return true;
+    }
     static_assert(covers(), "the intervals take every tap of every output once: SIZE taps an output");
+    static_assert(G::XV % 2 == 0 && G::XV >= G::M && G::TILE_W % 2 == 0,
+                  "whole store pairs, a disc's reach inside the staged columns");
+    static_assert(edges_valid(), "a stored column takes nothing from beyond the wave's ends");
     static_assert(SIZE != 67 || NCW * (2 * G::M + 1) == 402, "67 px: 402 taps per side pair");
     static_assert(firsts_start_intervals(), "firstR / firstL name an interval's first column");
     // issue priority over the steps DL ... 0: 3 at the first, 0 at the last
@@ -299,10 +344,21 @@ struct WSweep {
 #define WIDE_PRIO 1
 #endif
 
+// (lab switch, off in the product: 1 lets a chain wave issue the lead fetches of its NEXT phase in front of the phase barrier,
+// which it then crosses bare, and keep its phase state - ring slot, output rows - by increments.  Measured in round 14 and
+// not kept: the way from the barrier to the sweep falls from 93 to 46 instructions and the counters follow, the bench step
+// does not (-0.3 % and +0.2 % in two sessions, inside the runs' spread).  DESIGN.md K1 round 14, tools/valu_bound.py wide,
+// tools/ubench/tpi_lab.hip -DWIDE_BOUNDARY=1, profiles/r14_tpi67_boundary_stamps.txt.)
+#ifndef WIDE_BOUNDARY
+#define WIDE_BOUNDARY 0
+#endif
+
 // (lab switch: 1 stamps the clock around what a wave waits for at the end of a phase - a drain of the chain waves' output
 // stores (s_waitcnt vmcnt(0), which the compiler put there itself until round 10), then the barrier - summed per wave in
 // scalar registers and written by two blocks with ordinary stores when the kernel ends; 2 stamps the same points and
-// drains nothing, the kernel as it is built.  tools/ubench/tpi_lab.hip -DWIDE_STAMPS=1, profiles/r10_tpi67_store_drain.txt)
+// drains nothing, the kernel as it is built.  tools/ubench/tpi_lab.hip -DWIDE_STAMPS=1, profiles/r10_tpi67_store_drain.txt.
+// Round 14 adds the chain waves' way from the barrier to the sweep: a stamp where the lead rows have arrived, summed per wave
+// over the phases that sweep as its distance from the stamp behind the barrier.  profiles/r14_tpi67_boundary_stamps.txt)
 #ifndef WIDE_STAMPS
 #define WIDE_STAMPS 0
 #endif
@@ -317,8 +373,9 @@ struct WSweep {
 #define WIDE_STAGE_CEILING 0
 #endif
 #if WIDE_STAMPS
-constexpr int kWideStampBlocks = 2, kWideStampWaves = 11, kWideStampFields = 5;
-// per stamped block and wave: phases, ticks in all of them, in the drain, at the barrier, in a back-to-back stamp pair
+constexpr int kWideStampBlocks = 2, kWideStampWaves = 11, kWideStampFields = 7;
+// per stamped block and wave: phases, ticks in all of them, in the drain, at the barrier, in a back-to-back stamp pair; sweeps
+// that follow a barrier of the run, ticks from that barrier to the sweep's start
 __device__ unsigned long long wide_stamps[kWideStampBlocks][kWideStampWaves][kWideStampFields];
 __device__ __forceinline__ uint32_t wide_now() {  // (the low word: a phase is a few thousand ticks, a launch's sums fit)
     const uint32_t t = (uint32_t)__builtin_amdgcn_s_memtime();
@@ -332,11 +389,80 @@ typedef __attribute__((address_space(3))) const char lds_char;
 typedef __attribute__((address_space(1))) const u32x2w glb_u32x2w;
 typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 
-// Disc sums of the two output rows of a chain wave in ONE sweep (ring_disc_sum with 6 columns per lane, two rows): s0 is
-// the ring slot of Q index 0 of row A's window, acc[w][t] the sum of row w for the lane's column NCW lane + t (valid for
-// DL <= lane < 64 - DL), ctr[w][t] that pixel's own value.  The runs go in the order WGeo::S.order; fetch i loads the
-// prefix rows of the pair that no earlier fetch has loaded (WPair), and both rows' differences of a run are formed from
-// the loaded rows, the shared ones among them.
+// Fetch I of a pair's sweep: the bases it is the first to load through, then its rows.  b0 is the byte offset of the ring
+// slot of Q index 0 of row A's window, lb the lane's byte offset in a ring row.
+template <int SIZE, int R, int GR, int I>
+__device__ __forceinline__ void wide_pair_fetch(const uint32_t* ring, uint32_t b0, uint32_t lb,
+                                                u32x2w (&row)[WPair<SIZE, GR>::NK][3], uint32_t (&vb)[WPair<SIZE, GR>::T.nb]) {
+    using PT = WPair<SIZE, GR>;
+    constexpr uint32_t PB = (uint32_t)WGeo<SIZE>::W * 4;  // bytes per ring row
+    constexpr uint32_t RB = (uint32_t)R * PB;
+    lds_char* q = (lds_char*)ring;
+#pragma unroll
+    for (int b = 0; b < PT::T.nb; ++b)
+        if (PT::T.first[b] == I) {
+            const uint32_t d = b0 + (uint32_t)PT::T.kb[b] * PB;
+            vb[b] = lb + min(d, d - RB);  // the scalar wrap, then one vector add
+            asm("" : "+v"(vb[b]));        // (opaque: every read of the base keeps it and takes an immediate offset)
+        }
+#pragma unroll
+    for (int n = 0; n < PT::T.nload[I]; ++n) {
+        const int k = PT::T.load[I][n];
+        lds_char* pk = q + vb[PT::T.base[k]] + (uint32_t)(k - PT::T.kb[PT::T.base[k]]) * PB;
+        // (volatile: three ds_read_b64, not merged into ds_read2_b64, which banks 32 wide and moves half as many bytes a cycle)
+#pragma unroll
+        for (int h = 0; h < 3; ++h) row[k][h] = *(lds_u32x2w*)(pk + 8 * h);
+    }
+}
+
+// The lead fetches of a pair: the first LEAD fetches of its sweep, issued before the sweep starts - with WIDE_BOUNDARY in
+// front of the phase barrier (WPair::lead_is_published), so that the sweep behind it starts on registers already loading.
+// Their rows and bases, and nothing else of the sweep's, live from one phase to the next: lrow and lvb hold them in the order
+// loaded / formed (wide_lead_rows copies them to and from the sweep's own arrays; the copies are names, not instructions).
+template <int SIZE, int GR, int LEAD, bool OUT, class ROWS, class BASES>
+__device__ __forceinline__ void wide_lead_rows(ROWS& lrow, BASES& lvb, u32x2w (&row)[WPair<SIZE, GR>::NK][3],
+                                               uint32_t (&vb)[WPair<SIZE, GR>::T.nb]) {
+    using PT = WPair<SIZE, GR>;
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < LEAD && i < PT::NR; ++i)
+#pragma unroll
+        for (int m = 0; m < PT::T.nload[i]; ++m, ++n)
+#pragma unroll
+            for (int h = 0; h < 3; ++h) {
+                if (OUT) lrow[n][h] = row[PT::T.load[i][m]][h];
+                else row[PT::T.load[i][m]][h] = lrow[n][h];
+            }
+    int nb = 0;
+#pragma unroll
+    for (int b = 0; b < PT::T.nb; ++b)
+        if (PT::T.first[b] < LEAD) {
+            if (OUT) lvb[nb] = vb[b];
+            else vb[b] = lvb[nb];
+            ++nb;
+        }
+}
+
+template <int SIZE, int R, int GR, int LEAD>
+__device__ __forceinline__ void wide_pair_lead(const uint32_t* ring, uint32_t b0, int lane,
+                                               u32x2w (&lrow)[WPair<SIZE, GR>::lead_rows(LEAD)][3],
+                                               uint32_t (&lvb)[WPair<SIZE, GR>::lead_bases(LEAD)]) {
+    using PT = WPair<SIZE, GR>;
+    constexpr int NR = WGeo<SIZE>::NR;
+    const uint32_t lb = (uint32_t)lane * (NCW * 4);
+    u32x2w row[PT::NK][3];
+    uint32_t vb[PT::T.nb];
+    wide_static_for<(LEAD < NR ? LEAD : NR)>(
+        [&](auto I) { wide_pair_fetch<SIZE, R, GR, decltype(I)::value>(ring, b0, lb, row, vb); });
+    wide_lead_rows<SIZE, GR, LEAD, true>(lrow, lvb, row, vb);
+}
+
+// Disc sums of the two output rows of a chain wave in ONE sweep (ring_disc_sum with 6 columns per lane, two rows): b0 is
+// the byte offset of the ring slot of Q index 0 of row A's window, acc[w][t] the sum of row w for the lane's column
+// NCW lane + t (valid for DL <= lane < 64 - DL, and for the columns WGeo::XV admits of the lanes beside them), ctr[w][t]
+// that pixel's own value.  The runs go in the order WGeo::S.order; fetch i loads the prefix rows of the pair that no
+// earlier fetch has loaded (WPair), and both rows' differences of a run are formed from the loaded rows, the shared ones
+// among them.
 // PRIO (WIDE_PRIO, on): the wave's issue priority goes 3 -> 2 -> 1 -> 0 over the sweep's steps (CHAIN_PRIO,
 // disc_wave_impl.hpp), the counterpart of the 3 -> 2, 1 -> 0 pair that made the two chain waves of a SIMD advance together
 // when each summed its two rows one after the other.  A SIMD serves the higher priority first and among equals the older
@@ -350,43 +476,30 @@ typedef __attribute__((address_space(3))) const volatile u32x2w lds_u32x2w;
 // wave leaves the sweep at 0 - the finalisation and the stores run there - and a wave that sweeps nothing in a phase never
 // raised itself.  A compile-time choice, and no branch in the sweep either way: a DPP move and the add it feeds fold into
 // one DPP add only within a basic block.
-template <int SIZE, int R, int GR, int LEAD, bool PRIO>
-__device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, int s0, int lane, uint32_t (&acc)[2][NCW], uint32_t (&ctr)[2][NCW]) {
+// (LEAD_DONE: the caller has issued the lead fetches - wide_pair_lead with this b0 - into row and vb)
+template <int SIZE, int R, int GR, int LEAD, bool PRIO, bool LEAD_DONE>
+__device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, uint32_t b0, int lane,
+                                              u32x2w (&lrow)[WPair<SIZE, GR>::lead_rows(LEAD)][3],
+                                              uint32_t (&lvb)[WPair<SIZE, GR>::lead_bases(LEAD)], uint32_t (&acc)[2][NCW],
+                                              uint32_t (&ctr)[2][NCW]
+#if WIDE_STAMPS
+                                              , uint32_t& t_sweep
+#endif
+) {
     using G = WGeo<SIZE>;
     using PT = WPair<SIZE, GR>;
     using SW_ = WSweep<SIZE>;
     constexpr int NR = G::NR;
     constexpr int DL = G::DL;
-    constexpr int M = G::M;
-    constexpr uint32_t PB = (uint32_t)G::W * 4;  // bytes per ring row
-    constexpr uint32_t RB = (uint32_t)R * PB;
-    u32x2w row[PT::NK][3];
     // pR[w][D][t], pL[w][D][t]: what the lane's own columns give step D of row w's right / left chain for output t, summed
     // run by run as the differences are formed (a difference goes into every step that takes it at once and is not
     // kept: one sweep holds the open steps' sums of two rows, not two rows' differences of the runs in flight)
     uint32_t pR[2][DL + 1][NCW], pL[2][DL + 1][NCW];
     uint32_t aR[2][NCW], aL[2][NCW];
+    u32x2w row[PT::NK][3];
     uint32_t vb[PT::T.nb];
-    lds_char* q = (lds_char*)ring;
-    const uint32_t b0 = (uint32_t)s0 * PB, lb = (uint32_t)lane * (NCW * 4);
-    auto fetch = [&](auto I) {
-        constexpr int i = decltype(I)::value;
-#pragma unroll
-        for (int b = 0; b < PT::T.nb; ++b)
-            if (PT::T.first[b] == i) {
-                const uint32_t d = b0 + (uint32_t)PT::T.kb[b] * PB;
-                vb[b] = lb + min(d, d - RB);  // the scalar wrap, then one vector add
-                asm("" : "+v"(vb[b]));        // (opaque: every read of the base keeps it and takes an immediate offset)
-            }
-#pragma unroll
-        for (int n = 0; n < PT::T.nload[i]; ++n) {
-            const int k = PT::T.load[i][n];
-            lds_char* pk = q + vb[PT::T.base[k]] + (uint32_t)(k - PT::T.kb[PT::T.base[k]]) * PB;
-            // (volatile: three ds_read_b64, not merged into ds_read2_b64, which banks 32 wide and moves half as many bytes a cycle)
-#pragma unroll
-            for (int h = 0; h < 3; ++h) row[k][h] = *(lds_u32x2w*)(pk + 8 * h);
-        }
-    };
+    const uint32_t lb = (uint32_t)lane * (NCW * 4);
+    auto fetch = [&](auto I) { wide_pair_fetch<SIZE, R, GR, decltype(I)::value>(ring, b0, lb, row, vb); };
     // step D of the chains of both rows: the lane's own part, then the hop
     auto close = [&](auto DD) {
         constexpr int D = decltype(DD)::value;
@@ -425,7 +538,11 @@ __device__ __forceinline__ void wide_pair_sum(const uint32_t* ring, int s0, int 
         });
         RING_SB();
     };
-    wide_static_for<(LEAD < NR ? LEAD : NR)>([&](auto I) { fetch(I); });
+    if constexpr (LEAD_DONE) wide_lead_rows<SIZE, GR, LEAD, false>(lrow, lvb, row, vb);
+    else wide_static_for<(LEAD < NR ? LEAD : NR)>([&](auto I) { fetch(I); });
+#if WIDE_STAMPS
+    t_sweep = wide_now();  // (waits for the lead rows: the sweep's first subtract would)
+#endif
     if constexpr (PRIO) CHAIN_SETPRIO(3);
     static_assert(DL >= 1 && G::S.first_step[G::S.order[0]] == DL, "the first run opens the chains, the last step (D = 0) closes both");
     wide_static_for<NR>([&](auto J) {
@@ -486,7 +603,7 @@ template <int SIZE>
 __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(WaveArgs p, int tiles_x, int tiles_y, PartRun deal) {
     using G = WGeo<SIZE>;
     using C = WideCfg<SIZE>;
-    constexpr int B = C::B, R = C::R, PPT = C::PPT, SW = C::SW, NB_PRO = C::NB_PRO, DL = G::DL;
+    constexpr int B = C::B, R = C::R, PPT = C::PPT, SW = C::SW, NB_PRO = C::NB_PRO;
     constexpr unsigned kWindow = (1u << NB_PRO) - 1u;
     constexpr int kBad = 1, kFracOnly = 1 << 15;  // flag word: one field per batch history (the prologue shifts both)
     constexpr unsigned kHistMask = kWindow | kWindow * kFracOnly;
@@ -507,7 +624,7 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
     const int scol = 128 * wave + 2 * lane;  // a staging lane's first staged column (and the next one)
     int seen_tiles = 0, seen_frac = 0;
 #if WIDE_STAMPS
-    uint32_t ts_n = 0, ts_all = 0, ts_drain = 0, ts_bar = 0, ts_pair = 0, ts_prev = 0;
+    uint32_t ts_n = 0, ts_all = 0, ts_drain = 0, ts_bar = 0, ts_pair = 0, ts_prev = 0, ts_nsw = 0, ts_lead = 0;
 #endif
 
 #pragma unroll 1
@@ -628,16 +745,32 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         // bit k: batch (newest - k) holds a sample the chain cannot take; bit 15 + k: it holds a fractional sample (the
         // report only) - the flag word's two fields, shifted together
         unsigned hist = 0;
-        auto fold = [&](int parity) {
+        auto fold = [&](int parity, auto AT_ONCE) {
+            int f[SW];
+#pragma unroll
+            for (int w = 0; w < SW; ++w) f[w] = wflags[parity * SW + w];
+            // (the chain waves with WIDE_BOUNDARY: all the words read before any is combined - one round trip to LDS behind the
+            // barrier, not one a read, and one OR of three)
+            static_assert(SW == 3, "the flag words of the staging waves, held at once");
+            if constexpr (decltype(AT_ONCE)::value) asm("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]));
             int all = 0;
 #pragma unroll
-            for (int w = 0; w < SW; ++w) all |= wflags[parity * SW + w];
+            for (int w = 0; w < SW; ++w) all |= f[w];
             all = __builtin_amdgcn_readfirstlane(all);
             hist = ((hist << 1) | (unsigned)all) & kHistMask;
         };
 
         const int ocol = gx0 + lane * NCW;
-        const bool lane_ok = lane >= DL && lane < DL + G::NVL && ocol < p.nx;
+        // pair P of the lane's columns is stored when it lies among the strip's valid columns (WGeo::XV: the whole lanes, the
+        // last pair of the lane in front of them and the first pair of the lane behind) and in the raster (nx % 4 == 0, ocol
+        // even: a pair is inside or outside).  Invariant over the run: masks in scalar registers, no test in the phase loop.
+        bool pair_ok[NCW / 2];
+        bool lane_ok = false;
+#pragma unroll
+        for (int P = 0; P < NCW / 2; ++P) {
+            pair_ok[P] = lane * NCW + 2 * P >= G::XV && lane * NCW + 2 * P < G::W - G::XV && ocol + 2 * P < p.nx;
+            lane_ok = lane_ok || pair_ok[P];
+        }
         __syncthreads();  // (the previous run's chain waves are done with the ring and the flag words)
         // The run's prologue and phases, once for the staging waves and once for the chain waves: the same barriers on both
         // sides, and the batch a staging wave holds in registers from one phase to the next (va) is no live value in the
@@ -665,6 +798,49 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             for (int w = 0; w < SW; ++w) all |= wflags[w];
             hist = (unsigned)__builtin_amdgcn_readfirstlane(all) & kHistMask;
         }
+
+        // A chain wave's pair of the phase (WIDE_BOUNDARY): its first row, that row's offset in the output plane and the byte
+        // offset of the ring slot of Q index 0 of its window go on from phase to phase by scalar increments, and the rows and
+        // bases of the lead fetches live across the barrier.
+        using PT = WPair<SIZE, C::GR>;
+        constexpr uint32_t PB = (uint32_t)G::W * 4, RB = (uint32_t)R * PB;
+        constexpr bool kAhead = !stg && WIDE_BOUNDARY != 0;
+        static_assert(C::RPW == 2, "a chain wave sums its two rows of a phase in one sweep");
+        static_assert(!kAhead || PT::template lead_is_published<WIDE_LEAD, B>(),
+                      "the lead fetches read rows published a barrier earlier");
+        static_assert(C::PAD - 1 + B - C::RPW < R, "a run's first slots need no wrap");
+        const int pj = stg ? 0 : (wave - SW) * C::RPW;  // first row of the pair in the phase
+        [[maybe_unused]] int py = oyS + pj;
+        [[maybe_unused]] long long prow = (long long)(py - p.out_row0) * p.nx;
+        [[maybe_unused]] uint32_t pb0 = (uint32_t)(C::PAD - 1 + pj) * PB;
+        [[maybe_unused]] u32x2w row[PT::lead_rows(WIDE_LEAD)][3];
+        [[maybe_unused]] uint32_t vbase[PT::lead_bases(WIDE_LEAD)];
+        if constexpr (kAhead) {
+            if (nphase > 0) wide_pair_lead<SIZE, R, C::GR, WIDE_LEAD>(Q, pb0, lane, row, vbase);
+        }
+#if WIDE_STAMPS
+        [[maybe_unused]] uint32_t t_sweep = 0;
+#endif
+        // one row of the pair: finalised as tpi_march_kernel does, stored by pairs of columns
+        [[maybe_unused]] auto store_row = [&](bool row_ok, long long off, const uint32_t (&acc_k)[NCW],
+                                              const uint32_t (&ctr_k)[NCW]) {
+            if (lane_ok && row_ok) {
+                float out_t[NCW];
+#pragma unroll
+                for (int t = 0; t < NCW; ++t) {
+                    const int xi = (int)ctr_k[t];  // integers: see tpi_march_kernel
+                    out_t[t] = (float)((double)xi - (double)((int)acc_k[t] - xi) * inv_nm1);
+                }
+                // (the row's six values are formed HERE, under the one test of lane and row: left to itself the compiler sinks
+                // each pair's float64 arithmetic behind that pair's mask, a branch a pair)
+#pragma unroll
+                for (int t = 0; t < NCW; ++t) asm volatile("" : "+v"(out_t[t]));
+#pragma unroll
+                for (int P = 0; P < NCW / 2; ++P)
+                    if (__builtin_expect(pair_ok[P], true))  // (the address per pair: ocol < 0 in the lane in front of strip 0)
+                        *reinterpret_cast<float2*>(p.tpi + (off + ocol + 2 * P)) = make_float2(out_t[2 * P], out_t[2 * P + 1]);
+            }
+        };
 
         bool tile_frac = false;
 #pragma unroll 1
@@ -698,31 +874,43 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
                 if constexpr (WIDE_PRIO != 0) CHAIN_SETPRIO(0);
                 load_batch(C::PRO + (ph + 1) * B, va);
             } else if (compute) {
-                static_assert(C::RPW == 2, "a chain wave sums its two rows of a phase in one sweep");
-                const int j = (wave - SW) * C::RPW;  // first row of the pair in the phase
-                const int oy = oyA + j;
-                // A pair with a row in the output range is summed whole and the other row's store masked: no branch inside
-                // the sweep.  The masked row reads ring rows of this phase's window like its partner, and the staging has
-                // written the whole window of a phase that is computed (rows outside the raster as zeros).
-                if (oy + C::RPW > p.out_row0 && oy < p.out_row0 + p.out_rows) {
-                    const int s0 = (C::PAD - 1 + ph * B + j) % R;  // slot of Q index 0 of the first row's window
-                    uint32_t acc[C::RPW][NCW], ctr[C::RPW][NCW];
-                    wide_pair_sum<SIZE, R, C::GR, WIDE_LEAD, WIDE_PRIO != 0>(Q, s0, lane, acc, ctr);
+                if constexpr (kAhead) {
+                    // A pair with a row in the output range is summed whole and the other row's store masked: no branch inside
+                    // the sweep.  The masked row reads ring rows of this phase's window like its partner, and the staging has
+                    // written the whole window of a phase that is computed (rows outside the raster as zeros).
+                    if (py + C::RPW > p.out_row0 && py < p.out_row0 + p.out_rows) {
+                        uint32_t acc[C::RPW][NCW], ctr[C::RPW][NCW];
+                        wide_pair_sum<SIZE, R, C::GR, WIDE_LEAD, WIDE_PRIO != 0, true>(Q, pb0, lane, row, vbase, acc, ctr
+#if WIDE_STAMPS
+                                                                                       , t_sweep
+#endif
+                        );
 #pragma unroll
-                    for (int k = 0; k < C::RPW; ++k) {
-                        const bool row_ok = oy + k >= p.out_row0 && oy + k < p.out_row0 + p.out_rows;
-                        if (lane_ok && row_ok) {
-                            float* o = p.tpi + (size_t)(oy + k - p.out_row0) * p.nx + ocol;
-                            float out_t[NCW];
+                        for (int k = 0; k < C::RPW; ++k)
+                            store_row(py + k >= p.out_row0 && py + k < p.out_row0 + p.out_rows, prow + (long long)k * p.nx,
+                                      acc[k], ctr[k]);
+#if WIDE_STAMPS
+                        if (ph > 0) ts_nsw += 1, ts_lead += t_sweep - ts_prev;
+#endif
+                    }
+                } else {
+                    // (round 13's phase: slot, rows and lead fetches formed here, behind the barrier)
+                    const int oy = oyA + pj;
+                    if (oy + C::RPW > p.out_row0 && oy < p.out_row0 + p.out_rows) {
+                        const int s0 = (C::PAD - 1 + ph * B + pj) % R;  // slot of Q index 0 of the first row's window
+                        uint32_t acc[C::RPW][NCW], ctr[C::RPW][NCW];
+                        wide_pair_sum<SIZE, R, C::GR, WIDE_LEAD, WIDE_PRIO != 0, false>(Q, (uint32_t)s0 * PB, lane, row, vbase, acc, ctr
+#if WIDE_STAMPS
+                                                                                        , t_sweep
+#endif
+                        );
 #pragma unroll
-                            for (int t = 0; t < NCW; ++t) {
-                                const int xi = (int)ctr[k][t];  // integers: see tpi_march_kernel
-                                out_t[t] = (float)((double)xi - (double)((int)acc[k][t] - xi) * inv_nm1);
-                            }
-#pragma unroll
-                            for (int P = 0; P < NCW / 2; ++P)  // (nx % 4 == 0, ocol even: a pair is inside or outside)
-                                if (ocol + 2 * P < p.nx) *reinterpret_cast<float2*>(o + 2 * P) = make_float2(out_t[2 * P], out_t[2 * P + 1]);
-                        }
+                        for (int k = 0; k < C::RPW; ++k)
+                            store_row(oy + k >= p.out_row0 && oy + k < p.out_row0 + p.out_rows, (long long)(oy + k - p.out_row0) * p.nx,
+                                      acc[k], ctr[k]);
+#if WIDE_STAMPS
+                        if (ph > 0) ts_nsw += 1, ts_lead += t_sweep - ts_prev;
+#endif
                     }
                 }
             }
@@ -732,7 +920,35 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             if constexpr (!stg && WIDE_STAMPS == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const uint32_t t1 = wide_now();
 #endif
-            __syncthreads();
+            if constexpr (kAhead) {
+                // the next phase's pair: its state by increments (one conditional subtract for the ring's wrap), then its lead
+                // fetches - rows that earlier barriers published (lead_is_published) - so that the sweep behind the barrier
+                // starts on registers already loading.  The run's last phase fetches nothing.
+                py += B;
+                prow += (long long)B * p.nx;
+                pb0 += (uint32_t)B * PB;
+                pb0 = pb0 >= RB ? pb0 - RB : pb0;
+                if (ph + 1 < nphase) {
+                    wide_pair_lead<SIZE, R, C::GR, WIDE_LEAD>(Q, pb0, lane, row, vbase);
+                } else {
+                    // (no instruction: the registers get new, undefined values, so that the ones the sweep has consumed are
+                    // dead behind it - else they would count as live round the loop on this path and be spilled over the sweep)
+#pragma unroll
+                    for (int n = 0; n < PT::lead_rows(WIDE_LEAD); ++n)
+#pragma unroll
+                        for (int h = 0; h < 3; ++h) asm volatile("" : "=v"(row[n][h]));  // (volatile: one value each)
+#pragma unroll
+                    for (int b = 0; b < PT::lead_bases(WIDE_LEAD); ++b) asm volatile("" : "=v"(vbase[b]));
+                }
+                // A chain wave writes nothing to LDS, so it has nothing to release: it crosses the barrier bare, with no wait
+                // for the reads just issued (__syncthreads would put s_waitcnt lgkmcnt(0) here and hand their latency to
+                // the last wave to arrive).  The ring and flag reads behind it stay behind it: the statement clobbers memory,
+                // and a wave's LDS operations are carried out in the order issued.  The sweep's own reads have all been
+                // waited for by the finalisation, so the staging waves may write their slots behind this barrier as before.
+                asm volatile("s_barrier" ::: "memory");
+            } else {
+                __syncthreads();
+            }
 #if WIDE_STAMPS
             const uint32_t t2 = wide_now(), t3 = wide_now();
             if (ph > 0) {  // (a run's first phase has no phase before it to measure from)
@@ -744,7 +960,7 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
             }
             ts_prev = t2;
 #endif
-            fold((ph + 1) & 1);
+            fold((ph + 1) & 1, std::bool_constant<kAhead>{});
         }
         if constexpr (stg) {
             // The last phase's loads (the batch behind the run, clamped rows, never staged) are taken up HERE, so that no
@@ -768,6 +984,7 @@ __global__ __launch_bounds__(WideCfg<SIZE>::NW * 64) void tpi_ring_wide_kernel(W
         unsigned long long* o = wide_stamps[vb == 0 ? 0 : 1][wave];
         o[0] = (unsigned long long)ts_n, o[1] = (unsigned long long)ts_all, o[2] = (unsigned long long)ts_drain;
         o[3] = (unsigned long long)ts_bar, o[4] = (unsigned long long)ts_pair;
+        o[5] = (unsigned long long)ts_nsw, o[6] = (unsigned long long)ts_lead;
     }
 #endif
     if (p.report != nullptr && vb == nb / 2 && threadIdx.x == 0) {
