@@ -186,6 +186,27 @@ int topo_amd_halo_rows(int descriptor, double p0, double p1, int* above, int* be
 int topo_amd_tpi_std_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int size,
                          int out_row0, int out_rows, float* tpi_out, float* std_out);
 
+/* Valid-sample TPI / STD: the statistics of the samples that EXIST in the disc (numpy's nanmean / nanstd reading; no
+ * reference counterpart - its FFT turns one NaN into a NaN array, and fill_na invents terrain).  Either output may be NULL.
+ * Semantics.  The disc D(p) holds exactly the tap offsets topo_amd_tpi_std_dev uses for `size` (topo_amd_disc_mask as
+ * scipy.signal.convolve(..., "same") sees it, even sizes and the square below 5 included).  A tap is VALID when it lies
+ * inside the gny x nx raster and its sample is not MISSING (not finite, or beyond +-2^24: the definition above); nothing is
+ * padded with zeros.  Over the valid taps of a pixel: n their number, s1 = sum x, s2 = sum trunc(x)^2 (the int32-truncation
+ * quirk stays: where every tap is valid STD equals topo_amd_tpi_std_dev's); n' and s1' are n and s1 without the tap TPI
+ * excludes (kernel[size / 2][size / 2]).
+ *     TPI = x(p) - s1' / n'                              NaN where x(p) is missing or n' < max(1, min_count)
+ *     STD = sqrt(max(0, (s2 - s1^2 / n) / (n - 1)))      NaN where x(p) is missing or n  < max(2, min_count)
+ * Arithmetic.  The sums are exact integers - trunc(x) around an integer tile offset, fractional parts in units of 2^-16 m,
+ * the count an integer - and the closing formula is evaluated in float64 on the device and rounded to float32 once, so the
+ * bits do not depend on tiles, row blocks or out_row0 / out_rows.  A tile holding a valid sample beyond +-2^18, or more
+ * relief around its offset than 32-bit window sums of squares take (6521 m: -9999 left finite next to terrain), is summed
+ * tap by tap in 64 bits instead (slower, the same bits; reported by topo_amd_disc_route).
+ * Row blocks: ghost rows as topo_amd_halo_rows(TOPO_AMD_DESC_TPI, size, 0) gives them; rows beyond gny are outside the
+ * raster.  There is no pre-smoothing in this mode (a Gaussian over gaps needs a normalised convolution of its own).
+ * size 1 ... 101; larger sizes: TOPO_AMD_EUNSUP.  size < 1, min_count < 1 or both outputs NULL: TOPO_AMD_EINVAL.            */
+int topo_amd_tpi_std_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int size, int min_count,
+                               int out_row0, int out_rows, float* tpi_out, float* std_out);
+
 /* TPI for several disc sizes of one resident block (the scale loop of compute_tpi, reference
  * topo.py:132-141, and of scripts/compute_topo_descriptors.py:25-38): sizes that have a two-disc
  * kernel (pairs out of 5, 7, 9, 11 px) are evaluated two at a time from ONE pass over the DEM,
@@ -343,7 +364,11 @@ int topo_amd_gradient_route(int* route);
  *   bit 23       the call was split by rows (more rows than one launch covers).
  *   bit 24       the value of topo_amd_tpi_route.
  *   bit 25       launcher 4: the float64 planes (a sample that is not finite or beyond +-65536).
- *   bit 26       launcher 4: the narrow planes' kernel with the plane of fractional parts.                                */
+ *   bit 26       launcher 4: the narrow planes' kernel with the plane of fractional parts.
+ * The valid-sample calls (topo_amd_tpi_std_valid_dev / _raw / _packed) report launcher 6 in bits 0 - 2 (csrc/disc_valid.hip),
+ * bits 3 / 4, the tile height in bits 16 - 22, bit 23, and
+ *   bit 27       at least one tile of the call took the exact slow form (tap by tap, 64-bit sums).  This bit is the
+ *                kernels' word: topo_amd_disc_route waits for the compute stream to read it.                              */
 int topo_amd_disc_route(int* route);
 /* Mean and population standard deviation (numpy's default ddof = 0) of count device floats,
  * accumulated in float64.                                                                */
@@ -476,6 +501,10 @@ int topo_amd_std_raw(const topo_amd_raster* src, int ny, int nx, int size, doubl
 int topo_amd_tpi_std_raw(const topo_amd_raster* src, int ny, int nx, int size, double sigma, float* tpi_out, float* std_out);
 int topo_amd_tpi_std_multi_raw(const topo_amd_raster* src, int ny, int nx, int n_scales, const int32_t* sizes,
                                const double* sigmas, float* const* tpi_outs, float* const* std_outs);
+/* topo_amd_tpi_std_valid_dev on a host raster, through the upload / decode / row-chunk pipeline of topo_amd_tpi_std_raw: a
+ * declared nodata is NaN behind the decode, hence missing.  Either output may be NULL.                                     */
+int topo_amd_tpi_std_valid_raw(const topo_amd_raster* src, int ny, int nx, int size, int min_count, float* tpi_out,
+                               float* std_out);
 int topo_amd_gauss_raw(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, float* out);
 int topo_amd_sobel_raw(const topo_amd_raster* src, int ny, int nx, float* dx_out, float* dy_out);
 int topo_amd_fill_na_raw(const topo_amd_raster* src, int ny, int nx, const double* x_coords, double min_elevation, float* out,
@@ -560,6 +589,10 @@ int topo_amd_tpi_std_packed(const topo_amd_raster* src, int ny, int nx, int size
                             topo_amd_plane* std_out);
 int topo_amd_tpi_std_multi_packed(const topo_amd_raster* src, int ny, int nx, int n_scales, const int32_t* sizes,
                                   const double* sigmas, topo_amd_plane* tpi_outs, topo_amd_plane* std_outs);
+/* topo_amd_tpi_std_valid_raw with packed result planes: a NaN output (missing centre, too few valid taps) takes the plane's
+ * nodata code and is counted in `missing`.                                                                                */
+int topo_amd_tpi_std_valid_packed(const topo_amd_raster* src, int ny, int nx, int size, int min_count,
+                                  topo_amd_plane* tpi_plane, topo_amd_plane* std_plane);
 int topo_amd_gauss_packed(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, topo_amd_plane* out);
 int topo_amd_gradient_packed(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
                              const void* res_x, const void* res_y, topo_amd_plane* dx_out, topo_amd_plane* dy_out,

@@ -211,11 +211,15 @@ def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir=".", pack=None):
     return results
 
 
-def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=None):
+def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=None, skipna=False, min_count=1):
     hlp.check_dem(dem_ds)
     packing, = _lib.pack_list(pack, [want])
     scales = _as_list(scales)
     smth_factors = _as_list(smth_factors, len(scales))
+    if skipna and any(f is not None for f in smth_factors):
+        raise ValueError(f"compute_{want}: skipna=True takes no smoothing factor (a Gaussian over gaps needs a normalised "
+                         "convolution of its own)")
+    min_count = topo._skipna_args(skipna, min_count, None, f"compute_{want}")
     scales_pxl, _ = hlp.scale_to_pixel(scales, dem_ds)
     sigmas = hlp.get_sigmas(smth_factors, scales_pxl)
     name_of = _tpi_name if want == "tpi" else _std_name
@@ -234,7 +238,7 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=No
         # the partner's waits on the host for its turn - one extra host plane at most, and nothing computed is lost if a
         # later scale fails.
         partner, ahead = {}, {}
-        if want == "tpi":
+        if want == "tpi" and not skipna:  # (the valid-sample kernel takes its discs one by one)
             small = {}
             for k, (px, sigma) in enumerate(zip(scales_pxl, sigmas)):
                 if not sigma and int(px) in (5, 7, 9, 11):
@@ -262,11 +266,13 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=No
                 smooth = smooth or res.plane()
                 res.block.gaussian(sigma, sigma, smooth)
                 block = d.Block(smooth)
+            run = block.tpi_std_valid if skipna else block.tpi_std
+            valid_kw = {"min_count": min_count} if skipna else {}
             if want == "tpi":
-                block.tpi_std(int(px), tpi=out, **fin.rows_kw)
+                run(int(px), tpi=out, **valid_kw, **fin.rows_kw)
                 array = fin.leave(out, packing)
             else:
-                block.tpi_std(int(px), std=out, **fin.rows_kw)
+                run(int(px), std=out, **valid_kw, **fin.rows_kw)
                 array = fin.leave(out, packing)
                 if packing is None:
                     array = array.astype(np.float64)  # (packed: not widened)
@@ -281,17 +287,21 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=No
     return results
 
 
-def compute_tpi(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None):
-    """TPI for every scale (reference topo.py:88-141).  ``pack``, ``crop``, ``ind_nans``: see :func:`compute_dem`."""
+def compute_tpi(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None, skipna=False, min_count=1):
+    """TPI for every scale (reference topo.py:88-141).  ``pack``, ``crop``, ``ind_nans``: see :func:`compute_dem`.
+    ``skipna=True``: the mean of the samples that exist (``topo.tpi(skipna=True)``) - pass the DEM UNFILLED, its gaps as NaN
+    or as the declared fill value of a ``PackedDem``; ``min_count``: the valid taps a pixel needs.  No smoothing factor in
+    this mode (``ValueError``); output names are unchanged."""
     logger.info("***Starting TPI computation for scales %s meters***", scales)
-    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "tpi", pack)
+    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "tpi", pack, skipna, min_count)
 
 
-def compute_std(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None):
+def compute_std(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdir=".", pack=None, skipna=False, min_count=1):
     """Windowed standard deviation for every scale (reference topo.py:216-269).  ``pack``, ``crop``, ``ind_nans``: see
-    :func:`compute_dem`; a packed plane is not widened to float64."""
+    :func:`compute_dem`; a packed plane is not widened to float64.  ``skipna``, ``min_count``: see :func:`compute_tpi`
+    (``topo.std(skipna=True)``)."""
     logger.info("***Starting STD computation for scales %s meters***", scales)
-    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "std", pack)
+    return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "std", pack, skipna, min_count)
 
 
 def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdir=".", pack=None):

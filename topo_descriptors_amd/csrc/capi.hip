@@ -36,8 +36,19 @@ int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float*
     return launch_tpi_std(d, disc, tpi_out, std_out);
 }
 
+// TPI / STD over the valid samples of the disc (disc_valid.hip); the caller has taken the call's flag word (disc_valid_begin)
+int tpi_std_valid_block(const Block& b, int size, int min_count, float* tpi_out, float* std_out) {
+    TOPO_REQUIRE(size >= 1, "tpi_std_valid: disc size %d (at least 1)", size);
+    TOPO_REQUIRE(min_count >= 1, "tpi_std_valid: min_count %d (at least 1)", min_count);
+    TOPO_REQUIRE(tpi_out || std_out, "tpi_std_valid: both outputs are NULL");
+    DiscRuns disc;
+    TOPO_TRY(build_disc(size, &disc));
+    TOPO_TRY(check_block(b, -disc.dj_min, disc.dj_max, "tpi_std_valid"));
+    return launch_tpi_std_valid(b, disc, min_count, tpi_out, std_out);
+}
+
 namespace {
-thread_local int t_tpi_route = 0;     // 1: the calling thread's last TPI / STD disc call took the wide ring (topo_amd_tpi_route)
+thread_local int t_tpi_route = 0;    // 1: the calling thread's last TPI / STD disc call took the wide ring (topo_amd_tpi_route)
 thread_local int t_valley_route = 0;  // the evaluation the calling thread's last valley / ridge call took (topo_amd_valley_route)
 thread_local int t_valley_moments = 0;  // 1: that call formed the DEM's mean / std on the device (topo_amd_valley_moments_route)
 thread_local int t_sx_route = 0;      // the kernel route the calling thread's last Sx call took (topo_amd_sx_route)
@@ -88,6 +99,13 @@ int topo_amd_valley_moments_route(int* route) { return report_route(route, t_val
 int topo_amd_sx_route(int* route) { return report_route(route, t_sx_route, "sx_route"); }
 int topo_amd_gradient_route(int* route) { return report_route(route, t_gradient_route, "gradient_route"); }
 int topo_amd_disc_route(int* route) {  // (the wide-ring bit IS topo_amd_tpi_route)
+    if ((t_disc_route & kDiscLauncherMask) == kDiscValid) {
+        // the slow-form bit is the kernels' word: read from the device behind the call's launches
+        TOPO_ENTER();
+        int slow = 0;
+        TOPO_TRY(disc_valid_slow(&slow));
+        return report_route(route, (t_disc_route & ~kDiscValidSlow) | (slow ? kDiscValidSlow : 0), "disc_route");
+    }
     return report_route(route, (t_disc_route & ~kDiscWideRing) | (t_tpi_route ? kDiscWideRing : 0), "disc_route");
 }
 
@@ -171,6 +189,17 @@ int topo_amd_tpi_std_dev(const float* in, int in_rows, int in_row0, int gny, int
     forget_plane(tpi_out, out_rows, nx);
     forget_plane(std_out, out_rows, nx);
     return tpi_std_block(b, size, 0.0, tpi_out, std_out);
+}
+
+int topo_amd_tpi_std_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int size, int min_count, int out_row0,
+                               int out_rows, float* tpi_out, float* std_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
+    forget_plane(tpi_out, out_rows, nx);
+    forget_plane(std_out, out_rows, nx);
+    TOPO_TRY(disc_valid_begin());  // (one flag word per call; the arguments are checked with the block)
+    return tpi_std_valid_block(b, size, min_count, tpi_out, std_out);
 }
 
 int topo_amd_tpi_multi_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int n_sizes, const int32_t* sizes,

@@ -43,6 +43,7 @@ void release_raster_class();  // topo_amd_shutdown: every declaration, the DEM m
 // ---- capi.hip -------------------------------------------------------------------------------------------------------------
 inline float* shift(float* p, int rows, int nx) { return p ? p + (size_t)rows * nx : nullptr; }
 int tpi_std_block(const Block& b, int size, double sigma, float* tpi_out, float* std_out);
+int tpi_std_valid_block(const Block& b, int size, int min_count, float* tpi_out, float* std_out);
 // rows above / below an output row that the ray pixels n0 ... n1 - 1 of the Sx tables reach
 void sx_reach(const int32_t* dj, const double* dist, int n0, int n1, int* up, int* down);
 // x_coords (host, nx entries; NULL: the column index) must be finite and strictly monotonic; *ascending: their direction

@@ -87,9 +87,11 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
-constexpr int kWorkspaces = 16;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
-                                 // 14: a valley plane group's outputs, 15: the counters of the encode kernel)
+constexpr int kWorkspaces = 17;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
+                                 // 14: a valley plane group's outputs, 15: the counters of the encode kernel,
+                                 // 16: the slow-form flag words of the valid-sample disc kernel)
 constexpr int kEncodeCountsSlot = 15;
+constexpr int kDiscValidFlagSlot = 16;
 constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;
@@ -193,6 +195,13 @@ int launch_tpi_pair(const Block& b, int size_a, float* out_a, int size_b, float*
 bool tpi_pair_covers(int size_a, int size_b);
 // any size: float64 column prefix sums in HBM (slow, exact)
 int launch_disc_big(const Block& b, const DiscRuns& disc, float* tpi_out, float* std_out);
+// TPI / STD over the valid samples of the disc (disc_valid.hip): sizes 1 ... kDiscValidMaxSize, TOPO_AMD_EUNSUP beyond.
+// disc_valid_begin: in front of the launches of one call - takes the call's slow-form flag word and zeroes it on the compute
+// stream; disc_valid_slow: whether a tile of the calling thread's last such call took the slow form (waits for the stream).
+constexpr int kDiscValidMaxSize = 101;
+int launch_tpi_std_valid(const Block& b, const DiscRuns& disc, int min_count, float* tpi_out, float* std_out);
+int disc_valid_begin();
+int disc_valid_slow(int* slow);
 int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out);
 // ghost rows a row block carries above and below for the Gaussian of sigma: the radius, or 16 for the radii below 16
 // that take the matrix-core kernels (they want the accumulation-offset row of every 32-row tile inside the block)
@@ -238,7 +247,7 @@ void note_gradient_route(int route);  // what topo_amd_gradient_route reports fo
 // What topo_amd_disc_route reports for the calling thread (include/topo_amd.h has the layout).  The host code that picked
 // the kernels notes the word once its launches succeeded; the launchers around it put their own bits into the noted word.
 enum DiscRoute : int {
-    kDiscWave = 1, kDiscRepitched = 2, kDiscGather = 3, kDiscPlanes = 4, kDiscPair = 5, kDiscLauncherMask = 7,
+    kDiscWave = 1, kDiscRepitched = 2, kDiscGather = 3, kDiscPlanes = 4, kDiscPair = 5, kDiscValid = 6, kDiscLauncherMask = 7,
     kDiscTpi = 1 << 3, kDiscStd = 1 << 4,
     kDiscFirstGeneral = 0 << 5, kDiscFirstMarch = 1 << 5, kDiscFirstRing = 2 << 5, kDiscFirstWide = 3 << 5,
     kDiscFirstScaledAll = 4 << 5, kDiscFirstStdRing = 5 << 5, kDiscFirstSpec4 = 6 << 5, kDiscFirstSpec8 = 7 << 5,
@@ -247,7 +256,7 @@ enum DiscRoute : int {
     kDiscFracMarch = 1 << 10, kDiscFracRingBoth = 2 << 10, kDiscFracStdRingBoth = 3 << 10, kDiscFracSpecBoth = 4 << 10,
     kDiscScaledMarch = 1 << 13, kDiscDeferred = 1 << 14,
     kDiscTileShift = 16,  // bits 16 - 22: the tile height of the first kernel
-    kDiscSplit = 1 << 23, kDiscWideRing = 1 << 24, kDiscPlanesF64 = 1 << 25, kDiscPlanesFrac = 1 << 26,
+    kDiscSplit = 1 << 23, kDiscWideRing = 1 << 24, kDiscPlanesF64 = 1 << 25, kDiscPlanesFrac = 1 << 26, kDiscValidSlow = 1 << 27,
 };
 void note_disc_route(int route);
 int noted_disc_route();

@@ -517,6 +517,47 @@ int topo_amd_tpi_std_packed(const topo_amd_raster* raster, int ny, int nx, int s
                          });
 }
 
+// the same pipeline over the valid-sample kernel (disc_valid.hip): a declared nodata is NaN behind the decode, hence missing
+int topo_amd_tpi_std_valid_packed(const topo_amd_raster* raster, int ny, int nx, int size, int min_count, topo_amd_plane* tpi_plane,
+                                  topo_amd_plane* std_plane) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    Source src;
+    TOPO_TRY(make_source(raster, "tpi_std_valid", &src));
+    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std_valid: bad DEM");
+    TOPO_REQUIRE(size >= 1 && min_count >= 1, "tpi_std_valid: size %d, min_count %d (both at least 1)", size, min_count);
+    OutPlane tpi_out, std_out;
+    TOPO_TRY(make_out(tpi_plane, "tpi_std_valid", &tpi_out));
+    TOPO_TRY(make_out(std_plane, "tpi_std_valid", &std_out));
+    TOPO_REQUIRE(tpi_out || std_out, "tpi_std_valid: both outputs are NULL");
+    if (size > kDiscValidMaxSize) {
+        set_error("tpi_std_valid: disc size %d; the valid-sample kernel covers 1 ... %d", size, kDiscValidMaxSize);
+        return TOPO_AMD_EUNSUP;
+    }
+    const size_t bytes = (size_t)ny * nx * sizeof(float);
+    int above = 0, below = 0;
+    TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)size, 0.0, &above, &below));
+    HostRun run;
+    void *d_in = nullptr, *d_tpi = nullptr, *d_std = nullptr;
+    TOPO_TRY(run.alloc(&d_in, bytes));
+    if (tpi_out) TOPO_TRY(run.alloc(&d_tpi, bytes));
+    if (std_out) TOPO_TRY(run.alloc(&d_std, bytes));
+    run.prefault(tpi_out.host, tpi_out.bytes(ny, nx));
+    run.prefault(std_out.host, std_out.bytes(ny, nx));
+    TOPO_TRY(disc_valid_begin());  // one flag word for the launches of every row chunk
+    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {tpi_out.on((float*)d_tpi), std_out.on((float*)d_std)},
+                         [&](int view_rows, int r0, int rows) {
+                             Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
+                             return tpi_std_valid_block(b, size, min_count, shift((float*)d_tpi, r0, nx), shift((float*)d_std, r0, nx));
+                         });
+}
+
+int topo_amd_tpi_std_valid_raw(const topo_amd_raster* raster, int ny, int nx, int size, int min_count, float* tpi_out,
+                               float* std_out) {
+    topo_amd_plane t = f32_plane(tpi_out), s = f32_plane(std_out);
+    return topo_amd_tpi_std_valid_packed(raster, ny, nx, size, min_count, &t, &s);
+}
+
 int topo_amd_tpi_std_multi_packed(const topo_amd_raster* raster, int ny, int nx, int n_scales, const int32_t* sizes,
                                   const double* sigmas, topo_amd_plane* tpi_planes, topo_amd_plane* std_planes) {
     TOPO_ENTER();

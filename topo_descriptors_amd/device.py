@@ -244,7 +244,8 @@ def disc_route():
     two-disc kernel), bit 3 / 4 TPI / STD wanted, bits 5 - 8 the first kernel over the whole-metre tiles, bit 9 ``std_march``,
     bits 10 - 12 the second pass over fractional tiles, bit 13 ``scaled_march``, bit 14 the deferred general kernel, bits
     16 - 22 the first kernel's tile height, bit 23 split by rows, bit 24 ``tpi_route()``, bits 25 / 26 the float64 / the
-    fractional prefix planes."""
+    fractional prefix planes.  A valid-sample call (``skipna=True``, ``Block.tpi_std_valid``) reports launcher 6 with bits
+    3 / 4, 16 - 23 and bit 27: a tile took the exact slow form (read from the device: this call then waits for the stream)."""
     n = C.c_int32()
     _lib.check(_lib.lib().topo_amd_disc_route(C.byref(n)), "disc_route")
     return n.value
@@ -326,6 +327,15 @@ class Block:
         _lib.check(_lib.lib().topo_amd_tpi_std_dev(*self._head(), int(size), o0, on,
                                                    tpi.ptr if tpi else None,
                                                    std.ptr if std else None), "tpi_std_dev")
+
+    def tpi_std_valid(self, size, tpi=None, std=None, min_count=1, out_row0=None, out_rows=None):
+        """TPI and / or STD over the samples that exist in the disc (``topo_amd_tpi_std_valid_dev``; ``topo.tpi(skipna=True)``
+        for the rules): a missing sample or a tap outside the raster is left out of the sums and of their divisor.  Sizes
+        1 ... 101; ghost rows as for :meth:`tpi_std`."""
+        o0, on = self._range(out_row0, out_rows)
+        _lib.check(_lib.lib().topo_amd_tpi_std_valid_dev(*self._head(), int(size), int(min_count), o0, on,
+                                                         tpi.ptr if tpi else None,
+                                                         std.ptr if std else None), "tpi_std_valid_dev")
 
     def tpi_multi(self, sizes, outs, out_row0=None, out_rows=None):
         """TPI for several disc sizes; pairs of small sizes (5 ... 11 px) share one pass over the DEM

@@ -71,6 +71,34 @@ def _packed_tpi_std(values, size, sigma, packs, want):
     return out
 
 
+def _skipna_args(skipna, min_count, sigma, who):
+    """The arguments of the valid-sample mode, checked before the library is loaded; returns ``min_count`` as an int."""
+    if not skipna:
+        if min_count != 1:
+            raise ValueError(f"{who}: min_count belongs to skipna=True (without it every tap counts)")
+        return 1
+    if sigma:
+        raise ValueError(f"{who}: skipna=True takes no pre-smoothing (sigma={sigma!r}): a Gaussian over gaps needs a "
+                         "normalised convolution of its own")
+    if int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError(f"{who}: min_count {min_count!r} (a whole number of valid samples, at least 1)")
+    return int(min_count)
+
+
+def _valid_tpi_std(values, size, min_count, packs, want):
+    """``topo_amd_tpi_std_valid_packed``: the planes of ``want`` (tpi, std) over the valid samples of the disc, with the
+    packings ``packs`` (``None``: float32; an unpacked STD plane is widened to float64 as :func:`std` does)."""
+    keep, src, shape = _source(values)
+    made = [_lib.result_plane(q, shape) if w else None for q, w in zip(packs, want)]
+    refs = [C.byref(m[1]) if m else None for m in made]
+    _lib.check(_lib.lib().topo_amd_tpi_std_valid_packed(src, shape[0], shape[1], int(size), int(min_count), *refs),
+               "topo_amd_tpi_std_valid_packed")
+    out = [_lib.wrap_plane(*m, q) if m else None for m, q in zip(made, packs)]
+    if want[1] and packs[1] is None:
+        out[1] = out[1].astype(np.float64)
+    return out
+
+
 def _check_2d(a, who):
     if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError(f"{who}: expected a non-empty 2-D array, got shape {a.shape}")
@@ -92,7 +120,7 @@ def circular_kernel(size):
     return mask
 
 
-def tpi(dem, size, sigma=None, pack=None):
+def tpi(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     """Topographic position index: elevation minus the mean of the disc neighbourhood of
     diameter ``size`` pixels, centre excluded; optional Gaussian pre-smoothing ``sigma``
     (reference topo.py:145-181).  float32 in, float32 out; DataArray in, DataArray out.
@@ -111,9 +139,21 @@ def tpi(dem, size, sigma=None, pack=None):
     twice the time on such a DEM.
 
     ``pack``: a :class:`Packing` - the plane is encoded on the GPU and comes back as a :class:`PackedPlane` (never re-wrapped
-    into a DataArray), over the link at 1 or 2 bytes a sample; ``None``: float32 as ever."""
+    into a DataArray), over the link at 1 or 2 bytes a sample; ``None``: float32 as ever.
+
+    ``skipna=True``: the statistics of the samples that exist (numpy's ``nanmean`` reading; sizes 1 ... 101, no ``sigma``).
+    A tap counts when it lies inside the raster and its sample is not missing - nothing is padded with zeros, so the outer
+    ``size / 2`` pixels are unbiased, and a gap costs its own samples only.  With ``n'`` valid taps (the tap TPI excludes
+    left out) and ``s1'`` their sum, ``TPI = x - s1' / n'``; NaN where the pixel itself is missing or
+    ``n' < max(1, min_count)``.  The sums are exact integers (fractional parts in units of 2**-16 m), the closing formula is
+    float64 rounded to float32 once.  ``min_count`` without ``skipna`` is a ``ValueError``."""
+    min_count = _skipna_args(skipna, min_count, sigma, "tpi")
     values, rewrap = _unwrap(dem)
     _check_2d(values, "tpi")
+    if skipna:
+        packs = _lib.pack_list(pack, ["tpi"]) + [None]
+        out = _valid_tpi_std(values, size, min_count, packs, (True, False))[0]
+        return rewrap(out) if pack is None else out
     if pack is not None:
         return _packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi"]) + [None], (True, False))[0]
     keep, src, shape = _source(values)
@@ -124,12 +164,19 @@ def tpi(dem, size, sigma=None, pack=None):
     return rewrap(out)
 
 
-def std(dem, size, sigma=None, pack=None):
+def std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     """Sample standard deviation inside the disc window, with the reference's int32
     truncation of the squared term (reference topo.py:273-307).  Returns float64.  Non-finite samples: as for
-    :func:`tpi` (and :func:`dem` when ``sigma`` is given).  ``pack``: as for :func:`tpi`; a packed plane is not widened."""
+    :func:`tpi` (and :func:`dem` when ``sigma`` is given).  ``pack``: as for :func:`tpi`; a packed plane is not widened.
+
+    ``skipna=True`` (see :func:`tpi`): over the ``n`` valid taps of the disc, with ``s1`` their sum and ``s2`` the sum of
+    ``trunc(x)**2``, ``STD = sqrt(max(0, (s2 - s1**2 / n) / (n - 1)))`` - the value above wherever every tap is valid; NaN
+    where the pixel itself is missing or ``n < max(2, min_count)``."""
+    min_count = _skipna_args(skipna, min_count, sigma, "std")
     values, _ = _unwrap(dem)
     _check_2d(values, "std")
+    if skipna:
+        return _valid_tpi_std(values, size, min_count, [None] + _lib.pack_list(pack, ["std"]), (False, True))[1]
     if pack is not None:
         return _packed_tpi_std(values, size, sigma, [None] + _lib.pack_list(pack, ["std"]), (False, True))[1]
     keep, src, shape = _source(values)
@@ -140,12 +187,16 @@ def std(dem, size, sigma=None, pack=None):
     return out.astype(np.float64)
 
 
-def tpi_std(dem, size, sigma=None, pack=None):
+def tpi_std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     """TPI and STD of the same window in one pass over the DEM (no reference counterpart:
     the reference convolves three times for the pair).  ``pack``: one :class:`Packing` for both planes, or a pair / a dict
-    with the keys ``tpi`` and ``std`` (``None``: that plane stays float32, STD widened to float64)."""
+    with the keys ``tpi`` and ``std`` (``None``: that plane stays float32, STD widened to float64).  ``skipna``,
+    ``min_count``: as for :func:`tpi` and :func:`std`; both planes have the bits of the single calls."""
+    min_count = _skipna_args(skipna, min_count, sigma, "tpi_std")
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std")
+    if skipna:
+        return tuple(_valid_tpi_std(values, size, min_count, _lib.pack_list(pack, ["tpi", "std"]), (True, True)))
     if pack is not None:
         return tuple(_packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi", "std"]), (True, True)))
     keep, src, shape = _source(values)
