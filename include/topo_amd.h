@@ -202,7 +202,8 @@ int topo_amd_tpi_std_dev(const float* in, int in_rows, int in_row0, int gny, int
  * relief around its offset than 32-bit window sums of squares take (6521 m: -9999 left finite next to terrain), is summed
  * tap by tap in 64 bits instead (slower, the same bits; reported by topo_amd_disc_route).
  * Row blocks: ghost rows as topo_amd_halo_rows(TOPO_AMD_DESC_TPI, size, 0) gives them; rows beyond gny are outside the
- * raster.  There is no pre-smoothing in this mode (a Gaussian over gaps needs a normalised convolution of its own).
+ * raster.  There is no pre-smoothing in this call: smooth over the gaps with topo_amd_gaussian_valid_dev (the normalised
+ * convolution, below) and hand its plane to this one - topo.tpi(topo.dem(d, sigma, skipna=True), size, skipna=True).
  * size 1 ... 101; larger sizes: TOPO_AMD_EUNSUP.  size < 1, min_count < 1 or both outputs NULL: TOPO_AMD_EINVAL.            */
 int topo_amd_tpi_std_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int size, int min_count,
                                int out_row0, int out_rows, float* tpi_out, float* std_out);
@@ -227,6 +228,33 @@ int topo_amd_tpi_multi_dev(const float* in, int in_rows, int in_row0, int gny, i
 int topo_amd_gaussian_dev(const float* in, int in_rows, int in_row0, int gny, int nx,
                           double sigma_y, double sigma_x, int out_row0, int out_rows,
                           float* out);
+
+/* Valid-sample Gaussian: the normalised convolution of a DEM with gaps (csrc/gauss_valid.hip; no reference counterpart -
+ * ndimage.gaussian_filter lets one NaN spoil its whole window, and fill_na invents terrain).
+ * Semantics.  m(q) = 1 where sample q is valid, 0 where it is MISSING (not finite, or beyond +-2^24: the definition above, so
+ * a 1e20 sentinel is a gap).  w_y, w_x: exactly the taps of topo_amd_gaussian_dev - radius R = int(4 sigma + 0.5), normalised
+ * in float64 and rounded to float32; a sigma of 0 or a radius of 0 skips that axis; scipy's "reflect" at the edges of the
+ * GLOBAL raster, periodic, and a reflected tap is valid exactly when the sample it lands on is.
+ *     D(p) = sum_i sum_j w_y[i] w_x[j] m(q)              q = reflect(p + (i, j))
+ *     N(p) = sum_i sum_j w_y[i] w_x[j] m(q) x(q)
+ *     out(p) = N(p) / D(p)   where D(p) > 0, D(p) >= min_weight and (fill != 0 or m(p) = 1);   NaN elsewhere
+ * With min_weight = 0 and fill = 0 the output is NaN exactly at the missing pixels; with fill != 0 exactly where the reflected
+ * (2 R_y + 1) x (2 R_x + 1) window holds no valid sample - a two-dimensional gap interpolator.  weight_out (may be NULL)
+ * receives D(p) as float32 at every pixel, 0 where no tap is valid, whatever the NaN rule does to out.  On a gap-free raster D is
+ * 1 to rounding and out is topo_amd_gaussian_dev's value to 1e-3 m.
+ * Arithmetic.  N and D go through both 1-D passes and the division happens once, behind the second.  Each pass sums
+ * w m (x - c) and w m in float64 around an offset c taken on the global grid (N / D = c + sum w m (x - c) / sum w m for any
+ * finite c); between the passes N and D are rounded to float32 once each (N around the rounded D), the quotient once at the end.  Every term is
+ * bounded by D max|x - c| before the division, so a small D amplifies no rounding.  The bits do not depend on row blocks or
+ * out_row0 / out_rows.
+ * Row blocks: ghost rows as topo_amd_halo_rows(TOPO_AMD_DESC_GAUSS, sigma_y, 0) gives them (at least R); rows beyond gny do
+ * not exist - the filter reflects there.  The result is a plane topo_amd_tpi_std_valid_dev takes as it is: smooth over the
+ * gaps, then valid-sample TPI / STD.
+ * Radius 0 ... 121 per axis (sigma <= 30.25); beyond: TOPO_AMD_EUNSUP.  min_weight outside [0, 1] or NaN, a negative or NaN
+ * sigma, out NULL: TOPO_AMD_EINVAL.                                                                                        */
+int topo_amd_gaussian_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, double sigma_y, double sigma_x,
+                                double min_weight, int fill, int out_row0, int out_rows, float* out,
+                                float* weight_out /* may be NULL */);
 
 /* 3x3 Sobel pair / 8, true convolution, reflect (replaces topo.sobel topo.py:658-685).  */
 int topo_amd_sobel_dev(const float* in, int in_rows, int in_row0, int gny, int nx,
@@ -506,6 +534,11 @@ int topo_amd_tpi_std_multi_raw(const topo_amd_raster* src, int ny, int nx, int n
 int topo_amd_tpi_std_valid_raw(const topo_amd_raster* src, int ny, int nx, int size, int min_count, float* tpi_out,
                                float* std_out);
 int topo_amd_gauss_raw(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, float* out);
+/* topo_amd_gaussian_valid_dev (its semantics: D, N, out = N / D under min_weight and fill, weight_out = D or NULL) on a host
+ * raster, through the upload / decode / row-chunk pipeline of topo_amd_gauss_raw: a declared nodata is NaN behind the decode,
+ * hence a gap.  Errors as for the device call.                                                                            */
+int topo_amd_gauss_valid_raw(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, double min_weight,
+                             int fill, float* out, float* weight_out);
 int topo_amd_sobel_raw(const topo_amd_raster* src, int ny, int nx, float* dx_out, float* dy_out);
 int topo_amd_fill_na_raw(const topo_amd_raster* src, int ny, int nx, const double* x_coords, double min_elevation, float* out,
                          uint8_t* missing_out);
@@ -594,6 +627,10 @@ int topo_amd_tpi_std_multi_packed(const topo_amd_raster* src, int ny, int nx, in
 int topo_amd_tpi_std_valid_packed(const topo_amd_raster* src, int ny, int nx, int size, int min_count,
                                   topo_amd_plane* tpi_plane, topo_amd_plane* std_plane);
 int topo_amd_gauss_packed(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, topo_amd_plane* out);
+/* topo_amd_gauss_valid_raw with a packed result plane: a NaN output (a gap left open: D = 0, D < min_weight, or a missing
+ * pixel without fill) takes the plane's nodata code and is counted in `missing`.  weight_out stays float32 (or NULL).       */
+int topo_amd_gauss_valid_packed(const topo_amd_raster* src, int ny, int nx, double sigma_y, double sigma_x, double min_weight,
+                                int fill, topo_amd_plane* out, float* weight_out);
 int topo_amd_gradient_packed(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
                              const void* res_x, const void* res_y, topo_amd_plane* dx_out, topo_amd_plane* dy_out,
                              topo_amd_plane* slope_out, topo_amd_plane* aspect_out);

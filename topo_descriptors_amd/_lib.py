@@ -88,6 +88,10 @@ SIGNATURES = {
     "topo_amd_tpi_std_valid_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_int, C.c_int, _pp, _pp]),
     "topo_amd_gaussian_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                         C.c_double, C.c_int, C.c_int, _vp]),
+    "topo_amd_gaussian_valid_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                              C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "topo_amd_gauss_valid_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp]),
+    "topo_amd_gauss_valid_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _pp, _vp]),
     "topo_amd_sobel_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _vp, _vp]),
     "topo_amd_gradient_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,

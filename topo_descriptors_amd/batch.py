@@ -178,13 +178,16 @@ def _emit(array, dem_ds, name, crop, outdir, units, results):
     results[name] = array
 
 
-def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir=".", pack=None):
+def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir=".", pack=None, skipna=False, min_weight=0.0, fill=False):
     """Gaussian-smoothed DEM per scale, sigma = scale_px / CFG.scale_std (reference topo.py:16-59).  ``pack`` (here and in the
     other wrappers): a ``Packing`` - every plane is encoded on the GPU, leaves it at 1 or 2 bytes a sample, and is returned
     and saved as a ``PackedPlane`` (``write_output``); ``ind_nans`` then receive the fill code.  ``crop`` and ``ind_nans``
     (here and in the other wrappers) are applied on the GPU: only the rows of the domain are computed, only the domain is
     downloaded, returned and saved (``helpers.crop_window``: what ``Dataset.sel(crop)`` selects; no xarray needed), and
-    ``ind_nans`` - an index tuple as ``np.where`` gives it, or the boolean mask of ``fill_na_gpu`` - goes up once per call."""
+    ``ind_nans`` - an index tuple as ``np.where`` gives it, or the boolean mask of ``fill_na_gpu`` - goes up once per call.
+    ``skipna=True``: the Gaussian over the samples that exist (``topo.dem(skipna=True)``: pass the DEM UNFILLED) with its
+    ``min_weight`` and ``fill``; ``crop`` and ``ind_nans`` are applied afterwards as ever, output names are unchanged."""
+    min_weight = topo._valid_gauss_args(skipna, min_weight, fill, False, "compute_dem")
     packing, = _lib.pack_list(pack, ["dem"])
     hlp.check_dem(dem_ds)
     scales = _as_list(scales)
@@ -200,7 +203,10 @@ def compute_dem(dem_ds, scales, ind_nans=(), crop=None, outdir=".", pack=None):
         out = fin.plane()
         for scale, px in zip(scales, scales_pxl):
             sigma = px / CFG.scale_std
-            res.block.gaussian(sigma, sigma, out, **fin.rows_kw)
+            if skipna:
+                res.block.gaussian_valid(sigma, sigma, out, min_weight=min_weight, fill=fill, **fin.rows_kw)
+            else:
+                res.block.gaussian(sigma, sigma, out, **fin.rows_kw)
             _emit(fin.leave(out, packing), dem_ds, _dem_name(scale), crop, outdir, "m", results)
     finally:
         if out is not None:
@@ -217,8 +223,9 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=No
     scales = _as_list(scales)
     smth_factors = _as_list(smth_factors, len(scales))
     if skipna and any(f is not None for f in smth_factors):
-        raise ValueError(f"compute_{want}: skipna=True takes no smoothing factor (a Gaussian over gaps needs a normalised "
-                         "convolution of its own)")
+        raise ValueError(f"compute_{want}: skipna=True takes no smoothing factor: smooth over the gaps first, "
+                         f"topo.{want}(topo.dem(d, sigma, skipna=True), size, skipna=True) - or compute_dem(skipna=True) and "
+                         f"compute_{want}(skipna=True) on its planes")
     min_count = topo._skipna_args(skipna, min_count, None, f"compute_{want}")
     scales_pxl, _ = hlp.scale_to_pixel(scales, dem_ds)
     sigmas = hlp.get_sigmas(smth_factors, scales_pxl)
@@ -291,7 +298,8 @@ def compute_tpi(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdi
     """TPI for every scale (reference topo.py:88-141).  ``pack``, ``crop``, ``ind_nans``: see :func:`compute_dem`.
     ``skipna=True``: the mean of the samples that exist (``topo.tpi(skipna=True)``) - pass the DEM UNFILLED, its gaps as NaN
     or as the declared fill value of a ``PackedDem``; ``min_count``: the valid taps a pixel needs.  No smoothing factor in
-    this mode (``ValueError``); output names are unchanged."""
+    this mode (``ValueError``): pre-smoothing over gaps is the chain ``topo.tpi(topo.dem(d, sigma, skipna=True), size,
+    skipna=True)``, or ``compute_dem(skipna=True)`` first; output names are unchanged."""
     logger.info("***Starting TPI computation for scales %s meters***", scales)
     return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "tpi", pack, skipna, min_count)
 

@@ -13,7 +13,7 @@ NGROUPS = 16  # the per-size disc kernels: one source (disc_wave_group.hip), com
 UNITS = [("sx.hip", [], "sx.o"), ("gauss_f16.hip", [], "gauss_f16.o"), ("host_api.hip", [], "host_api.o"), ("shard.hip", [], "shard.o")] + \
         [("disc_wave_group.hip", [f"-DTOPO_GROUP={g}", f"-DTOPO_NGROUPS={NGROUPS}"], f"disc_wave_group{g}.o") for g in range(NGROUPS)] + \
         [(s, [], s.replace(".hip", ".o")) for s in ("disc_pair.hip", "disc.hip", "disc_valid.hip", "disc_wave.hip", "disc_big.hip", "gradient.hip",
-                                                    "gauss.hip", "valley.hip",
+                                                    "gauss.hip", "gauss_valid.hip", "valley.hip",
                                                     "moments_np.hip",
                                                     "valley_mfma.hip", "valley_fft.hip", "fill.hip", "decode.hip", "encode.hip",
                                                     "finish.hip", "raster_class.hip", "context.hip", "capi.hip")]

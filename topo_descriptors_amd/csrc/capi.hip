@@ -249,6 +249,21 @@ int topo_amd_gaussian_dev(const float* in, int in_rows, int in_row0, int gny, in
     return launch_gaussian(b, sigma_y, sigma_x, out);
 }
 
+int topo_amd_gaussian_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, double sigma_y, double sigma_x,
+                                double min_weight, int fill, int out_row0, int out_rows, float* out, float* weight_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(out != nullptr, "gaussian_valid: NULL output");
+    TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gaussian_valid: negative sigma");  // (false for NaN)
+    TOPO_REQUIRE(min_weight >= 0.0 && min_weight <= 1.0, "gaussian_valid: min_weight %g outside [0, 1]", min_weight);
+    Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
+    const int R = (int)std::min(4.0 * sigma_y + 0.5, kGaussValidMaxRadius + 1.0);  // (beyond it the launcher refuses the call)
+    TOPO_TRY(check_block(b, R, R, "gaussian_valid"));
+    forget_plane(out, out_rows, nx);
+    forget_plane(weight_out, out_rows, nx);
+    return launch_gaussian_valid(b, sigma_y, sigma_x, min_weight, fill != 0, out, weight_out);
+}
+
 int topo_amd_sobel_dev(const float* in, int in_rows, int in_row0, int gny, int nx, int out_row0,
                        int out_rows, float* dx_out, float* dy_out) {
     TOPO_ENTER();

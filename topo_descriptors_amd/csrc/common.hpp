@@ -87,11 +87,13 @@ struct GhostGate {
 };
 
 // ---- per-process context (one process drives one GPU) -------------------------------------
-constexpr int kWorkspaces = 17;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
+constexpr int kWorkspaces = 18;  // Context::ws slots (12: the fill's wide-row words, 13: the smoothed plane of a shard,
                                  // 14: a valley plane group's outputs, 15: the counters of the encode kernel,
-                                 // 16: the slow-form flag words of the valid-sample disc kernel)
+                                 // 16: the slow-form flag words of the valid-sample disc kernel,
+                                 // 17: the two-channel intermediate plane of the valid-sample Gaussian)
 constexpr int kEncodeCountsSlot = 15;
 constexpr int kDiscValidFlagSlot = 16;
+constexpr int kGaussValidSlot = 17;
 constexpr int kTables = 7;       // Context::tab slots (6: the fill's coordinates)
 struct Context {
     bool ready = false;
@@ -203,6 +205,11 @@ int launch_tpi_std_valid(const Block& b, const DiscRuns& disc, int min_count, fl
 int disc_valid_begin();
 int disc_valid_slow(int* slow);
 int launch_gaussian(const Block& b, double sigma_y, double sigma_x, float* out);
+// the normalised convolution over the valid samples (gauss_valid.hip): out = N / D where D > 0, D >= min_weight and (fill or
+// the pixel's own sample is valid), NaN elsewhere; weight (or nullptr) receives D.  Radii 0 ... kGaussValidMaxRadius per axis,
+// TOPO_AMD_EUNSUP beyond.
+constexpr int kGaussValidMaxRadius = 121;
+int launch_gaussian_valid(const Block& b, double sigma_y, double sigma_x, double min_weight, bool fill, float* out, float* weight);
 // ghost rows a row block carries above and below for the Gaussian of sigma: the radius, or 16 for the radii below 16
 // that take the matrix-core kernels (they want the accumulation-offset row of every 32-row tile inside the block)
 int gauss_ghost_rows(double sigma);

@@ -665,6 +665,44 @@ int topo_amd_gauss_packed(const topo_amd_raster* raster, int ny, int nx, double 
                          });
 }
 
+// the valid-sample Gaussian (gauss_valid.hip) through the same pipeline: a declared nodata is NaN behind the decode, hence a
+// gap; the weight plane is float32 whatever the packing of `plane`
+int topo_amd_gauss_valid_packed(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, double min_weight,
+                                int fill, topo_amd_plane* plane, float* weight_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    Source src;
+    TOPO_TRY(make_source(raster, "gauss_valid", &src));
+    OutPlane out, weight;
+    TOPO_TRY(make_out(plane, "gauss_valid", &out));
+    topo_amd_plane w = f32_plane(weight_out);
+    TOPO_TRY(make_out(&w, "gauss_valid", &weight));
+    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "gauss_valid: bad arguments");
+    TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gauss_valid: negative sigma");
+    TOPO_REQUIRE(min_weight >= 0.0 && min_weight <= 1.0, "gauss_valid: min_weight %g outside [0, 1]", min_weight);
+    const size_t bytes = (size_t)ny * nx * sizeof(float);
+    const int below = (int)std::min(4.0 * sigma_y + 0.5, kGaussValidMaxRadius + 1.0);  // the radius: all the ghost rows it wants
+    HostRun run;
+    void *d_in = nullptr, *d_out = nullptr, *d_weight = nullptr;
+    TOPO_TRY(run.alloc(&d_in, bytes));
+    TOPO_TRY(run.alloc(&d_out, bytes));
+    if (weight) TOPO_TRY(run.alloc(&d_weight, bytes));
+    run.prefault(out.host, out.bytes(ny, nx));
+    run.prefault(weight.host, weight.bytes(ny, nx));
+    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {out.on((float*)d_out), weight.on((float*)d_weight)},
+                         [&](int view_rows, int r0, int rows) {
+                             return topo_amd_gaussian_valid_dev((const float*)d_in, view_rows, 0, ny, nx, sigma_y, sigma_x, min_weight,
+                                                                fill, r0, rows, shift((float*)d_out, r0, nx),
+                                                                shift((float*)d_weight, r0, nx));
+                         });
+}
+
+int topo_amd_gauss_valid_raw(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, double min_weight,
+                             int fill, float* out, float* weight_out) {
+    topo_amd_plane o = f32_plane(out);
+    return topo_amd_gauss_valid_packed(raster, ny, nx, sigma_y, sigma_x, min_weight, fill, &o, weight_out);
+}
+
 int topo_amd_sobel_raw(const topo_amd_raster* raster, int ny, int nx, float* dx_out, float* dy_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());

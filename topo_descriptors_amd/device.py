@@ -353,6 +353,16 @@ class Block:
         _lib.check(_lib.lib().topo_amd_gaussian_dev(*self._head(), float(sigma_y), float(sigma_x),
                                                     o0, on, out.ptr), "gaussian_dev")
 
+    def gaussian_valid(self, sigma_y, sigma_x, out, weight=None, min_weight=0.0, fill=False, out_row0=None, out_rows=None):
+        """The Gaussian over the samples that exist (``topo_amd_gaussian_valid_dev``; ``topo.dem(skipna=True)`` for the
+        rules): ``out = N / D`` of the normalised convolution, NaN where ``D`` is 0 or below ``min_weight`` and - unless
+        ``fill`` - at the missing pixels; ``weight`` receives ``D``.  Radii 0 ... 121; ghost rows as for :meth:`gaussian`.
+        ``out`` is a plane :meth:`tpi_std_valid` takes as it is."""
+        o0, on = self._range(out_row0, out_rows)
+        _lib.check(_lib.lib().topo_amd_gaussian_valid_dev(*self._head(), float(sigma_y), float(sigma_x), float(min_weight),
+                                                          int(bool(fill)), o0, on, out.ptr,
+                                                          weight.ptr if weight else None), "gaussian_valid_dev")
+
     def gradient(self, sigma, res_x, res_y, sig_ratio=1.0, dx=None, dy=None, slope=None,
                  aspect=None, out_row0=None, out_rows=None):
         o0, on = self._range(out_row0, out_rows)

@@ -78,8 +78,8 @@ def _skipna_args(skipna, min_count, sigma, who):
             raise ValueError(f"{who}: min_count belongs to skipna=True (without it every tap counts)")
         return 1
     if sigma:
-        raise ValueError(f"{who}: skipna=True takes no pre-smoothing (sigma={sigma!r}): a Gaussian over gaps needs a "
-                         "normalised convolution of its own")
+        raise ValueError(f"{who}: skipna=True takes no pre-smoothing (sigma={sigma!r}): smooth over the gaps first, "
+                         f"{who}(dem(d, sigma, skipna=True), size, skipna=True)")
     if int(min_count) != min_count or int(min_count) < 1:
         raise ValueError(f"{who}: min_count {min_count!r} (a whole number of valid samples, at least 1)")
     return int(min_count)
@@ -146,7 +146,9 @@ def tpi(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     ``size / 2`` pixels are unbiased, and a gap costs its own samples only.  With ``n'`` valid taps (the tap TPI excludes
     left out) and ``s1'`` their sum, ``TPI = x - s1' / n'``; NaN where the pixel itself is missing or
     ``n' < max(1, min_count)``.  The sums are exact integers (fractional parts in units of 2**-16 m), the closing formula is
-    float64 rounded to float32 once.  ``min_count`` without ``skipna`` is a ``ValueError``."""
+    float64 rounded to float32 once.  ``min_count`` without ``skipna`` is a ``ValueError``.  Pre-smoothing in this mode is a
+    call of its own: ``tpi(dem(d, sigma, skipna=True), size, skipna=True)`` - the Gaussian over the gaps (:func:`dem`), then
+    this function on its plane; ``sigma=`` together with ``skipna=True`` stays a ``ValueError``."""
     min_count = _skipna_args(skipna, min_count, sigma, "tpi")
     values, rewrap = _unwrap(dem)
     _check_2d(values, "tpi")
@@ -171,7 +173,8 @@ def std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
 
     ``skipna=True`` (see :func:`tpi`): over the ``n`` valid taps of the disc, with ``s1`` their sum and ``s2`` the sum of
     ``trunc(x)**2``, ``STD = sqrt(max(0, (s2 - s1**2 / n) / (n - 1)))`` - the value above wherever every tap is valid; NaN
-    where the pixel itself is missing or ``n < max(2, min_count)``."""
+    where the pixel itself is missing or ``n < max(2, min_count)``.  Pre-smoothed: ``std(dem(d, sigma, skipna=True), size,
+    skipna=True)``, as for :func:`tpi`."""
     min_count = _skipna_args(skipna, min_count, sigma, "std")
     values, _ = _unwrap(dem)
     _check_2d(values, "std")
@@ -270,9 +273,36 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True, pack=No
 
 
 # ---- Gaussian, Sobel, gradient ------------------------------------------------------------------
-def dem(dem, sigma, pack=None):
+def _valid_gauss_args(skipna, min_weight, fill, return_weight, who):
+    """The arguments of the valid-sample Gaussian, checked before the DEM is touched or the library loaded; returns
+    ``min_weight`` as a float."""
+    if not skipna:
+        if min_weight != 0.0 or fill or return_weight:
+            raise ValueError(f"{who}: min_weight, fill and return_weight belong to skipna=True (without it the filter is "
+                             "ndimage.gaussian_filter's and has no weight)")
+        return 0.0
+    try:
+        mw = float(min_weight)
+    except (TypeError, ValueError):
+        mw = float("nan")
+    if not 0.0 <= mw <= 1.0:  # (false for NaN)
+        raise ValueError(f"{who}: min_weight {min_weight!r} (a share of the filter's weight, 0 ... 1)")
+    return mw
+
+
+def dem(dem, sigma, pack=None, skipna=False, min_weight=0.0, fill=False, return_weight=False):
     """Gaussian-smoothed DEM, reflect boundary, 4-sigma truncation (reference topo.py:62-80).
     ``sigma`` may be a scalar or an (axis0, axis1) pair.
+
+    ``skipna=True``: the Gaussian over the samples that exist - a normalised convolution.  With ``m`` 1 where a sample is
+    valid (finite and within +-2**24; a ``PackedDem``'s ``fill_value`` arrives as NaN) and the taps ``w`` of the plain filter,
+    ``D = sum w m`` and ``N = sum w m x`` over the reflected window, and the result is ``N / D`` where ``D > 0``,
+    ``D >= min_weight`` (0 ... 1: the share of the filter's weight that must rest on valid samples) and the pixel itself is
+    valid - or, with ``fill=True``, at the missing pixels too: a two-dimensional gap interpolator that leaves NaN only where
+    the whole window is empty.  NaN elsewhere.  ``return_weight=True`` returns ``(plane, weight)`` with ``weight = D`` as
+    float32.  Radii up to 121 (``sigma <= 30.25``).  The plane goes into :func:`tpi` / :func:`std` as it is:
+    ``tpi(dem(d, sigma, skipna=True), size, skipna=True)`` is the pre-smoothed TPI of a DEM with gaps.  Without ``skipna``
+    the kernels and bits are the ones described below, and ``min_weight``, ``fill``, ``return_weight`` are a ``ValueError``.
 
     Non-finite samples: a NaN / inf in the DEM makes non-finite every output whose window contains it, as in
     ``scipy.ndimage.gaussian_filter`` - and exactly those when the smoothing runs on the matrix cores (Gaussian radius
@@ -287,10 +317,21 @@ def dem(dem, sigma, pack=None):
     ``pack``: as for :func:`tpi`.  The :class:`PackedPlane` it gives is a source like any ``PackedDem``: a smoothed DEM packed
     to uint16 goes back into :func:`tpi` at 2 bytes a sample each way.
     """
+    min_weight = _valid_gauss_args(skipna, min_weight, fill, return_weight, "dem")
     values, rewrap = _unwrap(dem)
     _check_2d(values, "dem")
     sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (2,))
     keep, src, shape = _source(values)
+    if skipna:
+        packing, = _lib.pack_list(pack, ["dem"])
+        out, plane = _lib.result_plane(packing, shape)
+        weight = _plane(shape) if return_weight else None
+        _lib.check(_lib.lib().topo_amd_gauss_valid_packed(src, shape[0], shape[1], float(sig[0]), float(sig[1]), min_weight,
+                                                          int(bool(fill)), C.byref(plane),
+                                                          _lib.ptr(weight) if return_weight else None),
+                   "topo_amd_gauss_valid_packed")
+        out = rewrap(out) if packing is None else _lib.wrap_plane(out, plane, packing)  # (a packed plane is not re-wrapped)
+        return (out, weight) if return_weight else out
     if pack is not None:
         packing, = _lib.pack_list(pack, ["dem"])
         out, plane = _lib.result_plane(packing, shape)
