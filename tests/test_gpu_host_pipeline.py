@@ -1,7 +1,7 @@
 """The pipelined host-buffer path - what ``topo.tpi(ndarray)`` runs at real sizes (reference call shape: README.md:90,
 topo.py:138) - pinned against the device-resident call and the oracle.
 
-``run_pipelined`` (csrc/host_api.hip) only cuts a call into row chunks when the array holds three chunks or more; with the
+``HostCall::run`` (csrc/host_api.hip) only cuts a call into row chunks when the array holds three chunks or more; with the
 default 64 MB chunks no array of a test does.  Here ``TOPO_AMD_HOST_CHUNK_MB=1`` makes chunks of 960 rows (the minimum: whole
 tile rows of every kernel) and the DEMs have 3100 rows, so every call below runs in THREE chunks (960, 960, 1180 rows) - upload
 stream, compute stream, download stream, 2 x 3 events, the block views "the rows uploaded so far", a downloader thread or not - and

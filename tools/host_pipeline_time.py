@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-buffer calls (upload || kernels || download in row chunks, csrc/host_api.hip run_pipelined) against the serial order:
+"""Host-buffer calls (upload || kernels || download in row chunks, csrc/host_api.hip HostCall::run) against the serial order:
 topo_amd_tpi_f32 / topo_amd_gradient_f32 on an n x n DEM, page-locked and pageable arrays, for a few chunk sizes.
 Each configuration runs in a child process (a fresh set of device planes; the switches themselves are read at every call).
 

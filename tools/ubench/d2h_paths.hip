@@ -1,4 +1,4 @@
-// Which way does a device-to-host copy go, and how fast?  The pipelined host-buffer path (csrc/host_api.hip, run_pipelined) saw
+// Which way does a device-to-host copy go, and how fast?  The pipelined host-buffer path (csrc/host_api.hip, HostCall::run) saw
 // 64 MB D2H chunks on a copy-only stream run at 29 GB/s where one 1 GiB copy on the compute stream runs at 54 GB/s
 // (rocprofv3 --memory-copy-trace).  This bench times the candidates:
 //   build: hipcc --offload-arch=gfx950 -O2 -o d2h_paths.bin d2h_paths.hip        run: ./d2h_paths.bin

@@ -1,6 +1,6 @@
-// The order of operations of csrc/host_api.hip's run_pipelined on its own: H2D chunks on one stream, a small kernel per chunk
+// The order of operations of csrc/host_api.hip's HostCall::run on its own: H2D chunks on one stream, a small kernel per chunk
 // on a second, D2H chunks on a third - issued (A) all from one host thread, (B) with the downloads from a second thread
-// that waits on a condition variable, as run_pipelined did first.  Page-locked and pageable host memory.
+// that waits on a condition variable, as HostCall::run did first.  Page-locked and pageable host memory.
 //   hipcc --offload-arch=gfx950 -O2 -pthread -o pipe_paths.bin pipe_paths.hip
 #include <hip/hip_runtime.h>
 

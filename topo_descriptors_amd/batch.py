@@ -275,14 +275,10 @@ def _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, want, pack=No
                 block = d.Block(smooth)
             run = block.tpi_std_valid if skipna else block.tpi_std
             valid_kw = {"min_count": min_count} if skipna else {}
-            if want == "tpi":
-                run(int(px), tpi=out, **valid_kw, **fin.rows_kw)
-                array = fin.leave(out, packing)
-            else:
-                run(int(px), std=out, **valid_kw, **fin.rows_kw)
-                array = fin.leave(out, packing)
-                if packing is None:
-                    array = array.astype(np.float64)  # (packed: not widened)
+            run(int(px), **{want: out}, **valid_kw, **fin.rows_kw)
+            array = fin.leave(out, packing)
+            if want == "std" and packing is None:
+                array = array.astype(np.float64)  # (packed: not widened)
             _emit(array, dem_ds, name_of(scale, fact), crop, outdir, "m", results)
     finally:
         for plane in (out, smooth, second):

@@ -51,7 +51,7 @@ int check_fill_coords(const double* x, int nx, bool* ascending);
 void note_valley_moments(int route);  // what topo_amd_valley_moments_route reports for the calling thread
 
 // ---- host_api.hip ---------------------------------------------------------------------------------------------------------
-void prefault_pages(void* host, size_t bytes);  // HostRun::prefault on its own: returns when the pages are there
+void prefault_pages(void* host, size_t bytes);  // PageToucher::prefault on its own: returns when the pages are there
 
 // ---- shard.hip ------------------------------------------------------------------------------------------------------------
 int check_gate_errors();  // behind every call that synchronises: a lean-mode wait at the ghost-row gate that ran out

@@ -123,7 +123,7 @@ struct Context {
     // mapped memory ran at half the link's rate: profiles/r05_host_pipeline.txt).  topo_amd_release_host_planes frees them.
     std::vector<void*> host_planes;
     std::vector<size_t> host_plane_bytes;
-    hipStream_t up = nullptr, down = nullptr;  // the copies of a pipelined host-buffer call (host_api.hip, run_pipelined; created on first use)
+    hipStream_t up = nullptr, down = nullptr;  // the copies of a pipelined host-buffer call (host_api.hip, HostCall::run; created on first use)
     std::vector<hipEvent_t> pipe_events;        // its events: uploaded chunk k, computed chunk k
     hipStream_t aux = nullptr;       // bandwidth-bound epilogues running next to matrix-core kernels (created on first use)
     hipEvent_t aux_ready[64] = {};    // compute -> aux, one per chunk

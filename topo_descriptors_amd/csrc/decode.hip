@@ -1,6 +1,6 @@
 // K-decode: a raster as it is stored (int16 / uint16 / int32 / uint8 / float64, or float32 with a scale, an offset or a
 // nodata value) turned into the float32 plane every other kernel reads - decode_dev of decode.hpp per sample.  The host
-// pipeline (host_api.hip, run_pipelined) uploads the caller's bytes as they are and runs this on the upload stream behind each
+// pipeline (host_api.hip, HostCall::run) uploads the caller's bytes as they are and runs this on the upload stream behind each
 // row chunk's copy, so the single-threaded host cast in front of a call is gone and int16 rasters cross the link at half
 // the bytes.
 //

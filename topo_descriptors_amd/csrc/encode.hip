@@ -1,5 +1,5 @@
 // K-encode: a float32 result plane turned into the samples a file stores - int16 / uint16 / uint8 codes with a scale, an
-// offset and a nodata code, or binary16 - encode_dev of encode.hpp per sample.  The host pipeline (host_api.hip, run_pipelined)
+// offset and a nodata code, or binary16 - encode_dev of encode.hpp per sample.  The host pipeline (host_api.hip, HostCall::run)
 // runs this on the compute stream behind each row chunk's kernels and downloads the packed rows, so a result crosses the
 // link at a half or a quarter of the float32 bytes; decode.hip is its mirror on the upload side.
 //

@@ -17,23 +17,14 @@ namespace topo {
 namespace {
 
 thread_local int t_host_chunks = 0;  // row chunks of the calling thread's last host-buffer call (topo_amd_host_chunks)
-// Device buffers of one host-buffer call, and the preparation of its result arrays.  A result array
-// fresh from the allocator has no pages yet; faulting them in one by one under the download is what a
-// host-buffer call spends most of its time on (tools/ubench/page_touch.cpp: 92 ms per GiB against 19 ms
-// for the copy itself).  prefault() asks for huge pages and touches the array from a few threads
-// while the upload and the kernels run; ready() joins them before the first download.
-struct HostRun {
+// The device planes of one call: the k-th plane it asks for is the k-th plane of the context's pool (Context::host_planes),
+// grown when it must be.
+struct PlanePool {
     std::vector<void*> bufs;
-    std::vector<std::thread> touchers;
-    explicit HostRun(bool entry_point = true) {
-        if (entry_point) t_host_chunks = 0;
-    }
-    ~HostRun() {
-        ready();
+    std::vector<size_t> sizes;
+    ~PlanePool() {
         for (size_t k = 0; k < bufs.size(); ++k) dem_memo_forget(bufs[k], sizes[k]);  // (the planes stay; what was known about their content goes)
     }
-    std::vector<size_t> sizes;
-    // the k-th plane this call asks for is the k-th plane of the context's pool (Context::host_planes), grown when it must be
     int alloc(void** p, size_t bytes) {
         Context& c = ctx();
         const size_t k = bufs.size();
@@ -57,6 +48,14 @@ struct HostRun {
         dem_memo_forget(*p, c.host_plane_bytes[k]);  // (another call's data: nothing is known about this plane)
         return TOPO_AMD_OK;
     }
+};
+// The preparation of a call's result arrays.  A result array fresh from the allocator has no pages yet; faulting them in one
+// by one under the download is what a host-buffer call spends most of its time on (tools/ubench/page_touch.cpp: 92 ms per GiB
+// against 19 ms for the copy itself).  prefault() asks for huge pages and touches the array from a few threads while the
+// upload and the kernels run; ready() joins them before the first download.
+struct PageToucher {
+    std::vector<std::thread> touchers;
+    ~PageToucher() { ready(); }
     void prefault(void* host, size_t bytes) {
         constexpr uintptr_t kPage = 4096, kHuge = (uintptr_t)2 << 20;
         static const bool enabled = [] {
@@ -92,31 +91,37 @@ struct HostRun {
     }
 };
 
-// ---- upload || kernels || download in row chunks (VERDICT r04 item 5) -------------------------------------------------------
-// A host-buffer call used to be three serial steps - 18.7 ms up, 1.3 ms of kernels, 19.9 ms down for TPI 67 px on 16384^2 -
-// over a link that carries both directions at once (48.6 GB/s each way against 57 one way, profiles/r01_host_path.txt).  Row
-// blocks give the single block's bits, so the call is cut into row chunks: the calling thread uploads chunk k on one
-// stream and, as soon as the rows a chunk's outputs depend on are on the device, enqueues its kernels (on the block view
-// "the rows uploaded so far") on the compute stream; a second host thread downloads the output rows of every finished
-// chunk on a third stream (its own thread because copies to and from pageable memory block the caller).
-// TOPO_AMD_HOST_PIPELINE=0: one chunk (the old order).  TOPO_AMD_HOST_CHUNK_MB: size of a chunk of the DEM (default 64).
-// TOPO_AMD_HOST_DOWNLOADS=thread / inline: who issues the downloads (default: by the arrays, below).  All three are read at
-// every call (a getenv each), so a test can walk through them in one process.
+// One result plane of a host-buffer call: the caller's array - checked once, by make_plane() for a topo_amd_plane, or any
+// array of `elem` bytes a sample that is downloaded as the kernels write it (HostCall::stored) - and, once HostCall::add()
+// has bound it, its device planes.  host == nullptr: absent (a NULL struct or NULL data, where the call allows it).
 struct HostPlane {
-    void* host;
-    void* dev;
+    void* host = nullptr;
+    void* dev = nullptr;          // what is downloaded
     size_t elem = sizeof(float);  // bytes per sample (the missing mask of topo_amd_fill_na_f32: 1; a packed plane: 1 or 2)
     // A packed result plane (include/topo_amd.h): the kernels write the float32 device plane `f32`, its rows are encoded
-    // behind them into the packed device plane `dev` - taken from the pool by run_pipelined, behind every plane a float32
+    // behind them into the packed device plane `dev` - taken from the pool by HostCall::run, behind every plane a float32
     // call takes - and `dev` is what gets downloaded.  f32 == nullptr: a plane downloaded as the kernels write it.
     const float* f32 = nullptr;
     EncodeParams enc;
     topo_amd_plane* report = nullptr;  // the caller's struct: its counters are written after the last chunk
     void** pool = nullptr;             // a multi-scale call: where the packed device plane (2 bytes a sample) is kept between its scales
+    explicit operator bool() const { return host != nullptr; }
     bool packed() const { return host != nullptr && f32 != nullptr; }
+    size_t bytes(int ny, int nx) const { return (size_t)ny * nx * elem; }
     void* host_row(int r, int nx) const { return (char*)host + (size_t)r * nx * elem; }
     const void* dev_row(int r, int nx) const { return (const char*)dev + (size_t)r * nx * elem; }
 };
+int make_plane(topo_amd_plane* plane, const char* who, HostPlane* h) {
+    *h = HostPlane();
+    if (!plane || !plane->data) return TOPO_AMD_OK;
+    TOPO_TRY(make_encode(plane, who, &h->enc));
+    plane->missing = plane->saturated = 0;
+    h->host = plane->data;
+    h->elem = plane_sample_bytes(h->enc.dtype);
+    h->report = plane;
+    return TOPO_AMD_OK;
+}
+topo_amd_plane f32_plane(float* p) { return topo_amd_plane{p, TOPO_AMD_F32, 0, 1.0, 0.0, 0.0, 0, 0}; }
 int pipeline_chunk_rows(int ny, int nx) {
     const char* e = std::getenv("TOPO_AMD_HOST_PIPELINE");
     if (e && *e == '0') return ny;
@@ -127,14 +132,16 @@ int pipeline_chunk_rows(int ny, int nx) {
     rows = std::max(960L, rows / 960 * 960);
     return rows * 3 > ny ? ny : (int)rows;  // fewer than three chunks: nothing to overlap
 }
-// The cuts of a pipelined call: chunks of `chunk` rows, the last one half a chunk to a chunk and a half (no sliver at the end).
+// The row cuts of a call, chunk k being rows [cut[k], cut[k + 1]): {0, ny} for a call that is not cut (one_chunk, or what
+// pipeline_chunk_rows says), else chunks of that many rows, the last one half a chunk to a chunk and a half (no sliver at the
+// end) - three chunks at least.
 // (Round 6 tried a taper - a quarter and a half chunk at both ends, so that less stands in front of the first kernels and
 // behind the last ones: 16384^2 TPI 67 px 26.05 -> 25.93 ms page-locked, 24.97 -> 24.80 pageable, profiles/r06_host_pipeline.txt:
 // the fill and the drain are not what separates the call from the 22.4 ms of 1 GiB each way at 48 GB/s.  Not kept.)
-std::vector<int> pipeline_cuts(int ny, int chunk) {
+std::vector<int> row_cuts(int ny, int nx, bool one_chunk) {
+    const int chunk = one_chunk ? ny : pipeline_chunk_rows(ny, nx);
     std::vector<int> cut{0};
-    int at = 0;
-    while (ny - at > chunk + chunk / 2) cut.push_back(at += chunk);
+    for (int at = 0; chunk < ny && ny - at > chunk + chunk / 2;) cut.push_back(at += chunk);
     cut.push_back(ny);
     return cut;
 }
@@ -178,47 +185,14 @@ hipError_t enqueue_rows(const Source& s, char* d_raw, float* d_in, int r0, int r
 }
 // the raw plane of a call (nullptr for a source that needs none): the LAST plane a call takes from the pool, so the planes
 // of a float32 call are the ones they always were
-int raw_plane(HostRun& run, const Source& s, int ny, int nx, char** d_raw) {
+int raw_plane(PlanePool& pool, const Source& s, int ny, int nx, char** d_raw) {
     *d_raw = nullptr;
     if (s.as_stored) return TOPO_AMD_OK;
     void* p = nullptr;
-    TOPO_TRY(run.alloc(&p, (size_t)ny * nx * s.elem));
+    TOPO_TRY(pool.alloc(&p, (size_t)ny * nx * s.elem));
     *d_raw = (char*)p;
     return TOPO_AMD_OK;
 }
-
-// A caller's result plane as a host-buffer call sees it: a checked topo_amd_plane (absent: a NULL struct or NULL data, where
-// the call allows it).  Float32 planes are downloaded as the kernels write them, the others encoded first (HostPlane).
-struct OutPlane {
-    void* host = nullptr;
-    EncodeParams enc;
-    topo_amd_plane* report = nullptr;
-    explicit operator bool() const { return host != nullptr; }
-    size_t bytes(int ny, int nx) const { return (size_t)ny * nx * plane_sample_bytes(enc.dtype); }
-    // ... on the float32 device plane the kernels write; pool: see HostPlane
-    HostPlane on(float* dev, void** pool = nullptr) const {
-        HostPlane h{dev ? host : nullptr, dev};
-        if (h.host && !enc.plain()) {
-            h.dev = nullptr;
-            h.elem = plane_sample_bytes(enc.dtype);
-            h.f32 = dev;
-            h.enc = enc;
-            h.report = report;
-            h.pool = pool;
-        }
-        return h;
-    }
-};
-int make_out(topo_amd_plane* plane, const char* who, OutPlane* o) {
-    *o = OutPlane();
-    if (!plane || !plane->data) return TOPO_AMD_OK;
-    TOPO_TRY(make_encode(plane, who, &o->enc));
-    plane->missing = plane->saturated = 0;
-    o->host = plane->data;
-    o->report = plane;
-    return TOPO_AMD_OK;
-}
-topo_amd_plane f32_plane(float* p) { return topo_amd_plane{p, TOPO_AMD_F32, 0, 1.0, 0.0, 0.0, 0, 0}; }
 
 // The missing / saturated counters of the encode kernels: one pair per plane, in a workspace of their own.  reserve() zeroes
 // them on the compute stream, in front of the launches that get pair(q); fetch() enqueues their copy back; behind the caller's
@@ -260,19 +234,116 @@ int copy_streams(int n) {
     return TOPO_AMD_OK;
 }
 
-// compute(view_rows, out_row0, out_rows): enqueue the kernels that write output rows [out_row0, out_row0 + out_rows) of
-// every plane, reading rows [0, view_rows) of d_in.  below: rows of the DEM beneath an output row that it depends on.
-// upload == false: the DEM is on the device already (later scales of a multi-scale call).
-// src: the caller's raster (ignored when upload == false).  A source that is not float32-as-stored goes chunk by chunk into
-// a raw device plane and is decoded into d_in on the stream of the copy, in front of the event the kernels wait for.
-// one_chunk: the call is not cut, whatever TOPO_AMD_HOST_* say.
+// One host-buffer call, for as long as its entry point runs: the checked source, the shape, the device planes it takes from
+// the context's pool and its result planes.
+// POOL ORDER - pool slots only grow, so a changed order makes alternating calls reallocate, and copies out of fresh device
+// memory run at half rate.  A call takes: d_in (open), the wanted result planes in the order they are
+// registered (plane / stored / shared), the call's extras (extra), and in run() the raw plane of a source that is decoded on
+// the device, then the packed device planes.
 constexpr bool kRowChunks = false, kOneChunk = true;
+struct HostCall {
+    Source src;
+    int ny = 0, nx = 0;
+    const char* who = "";
+    float* d_in = nullptr;
+    PlanePool pool;     // (released behind the page threads: declared in front of them)
+    PageToucher pages;
+    std::vector<HostPlane> outs;
+    bool uploaded = false;  // the DEM is on the device: every run() but the first (the later scales of a multi-scale call)
+
+    // the source and the shape checked, the chunk counter reset, d_in taken
+    int open(const topo_amd_raster* raster, int rows, int cols, const char* name, const char* bad_shape = "bad DEM") {
+        who = name;
+        TOPO_TRY(make_source(raster, who, &src));
+        TOPO_REQUIRE(rows >= 1 && cols >= 1, "%s: %s", who, bad_shape);
+        ny = rows;
+        nx = cols;
+        t_host_chunks = 0;
+        return extra(&d_in);
+    }
+    size_t samples() const { return (size_t)ny * nx; }
+    template <class T>
+    int extra(T** p) {  // a device plane of ny x nx samples of T
+        void* q = nullptr;
+        TOPO_TRY(pool.alloc(&q, samples() * sizeof(T)));
+        *p = (T*)q;
+        return TOPO_AMD_OK;
+    }
+    // a checked plane on the device plane the kernels write for it (nullptr: not wanted); pool: see HostPlane
+    void add(HostPlane h, void* dev, void** packed_pool = nullptr) {
+        if (!dev) h.host = nullptr;
+        if (h.host && !h.enc.plain()) {
+            h.f32 = (const float*)dev;
+            h.pool = packed_pool;
+        } else {
+            h.dev = dev;
+        }
+        outs.push_back(h);
+    }
+    // registers a plane of the caller's: checked, its device plane taken (*dev; nullptr when the plane is absent), its pages
+    // being touched, in the list of what run() downloads
+    int plane(topo_amd_plane* p, float** dev) {
+        HostPlane h;
+        TOPO_TRY(make_plane(p, who, &h));
+        *dev = nullptr;
+        if (h) TOPO_TRY(extra(dev));
+        pages.prefault(h.host, h.bytes(ny, nx));
+        add(h, *dev);
+        return TOPO_AMD_OK;
+    }
+    // ... an array that takes the samples as the kernels write them: float32 only (sobel), the uint8 mask of fill_na
+    template <class T>
+    int stored(T* host, T** dev) {
+        *dev = nullptr;
+        if (host) TOPO_TRY(extra(dev));
+        in_place(host, *dev);
+        return TOPO_AMD_OK;
+    }
+    // ... on a device plane the call has already (fill_na fills d_in itself)
+    template <class T>
+    void in_place(T* host, T* dev) {
+        HostPlane h;
+        h.host = host;
+        h.elem = sizeof(T);
+        pages.prefault(host, h.bytes(ny, nx));
+        add(h, dev);
+    }
+    // ... planes that take turns on one device plane (the scales of a multi-scale call): that plane if any of them is wanted,
+    // the pages of all; each scale add()s its own in front of its run()
+    int shared(const std::vector<HostPlane>& planes, float** dev) {
+        *dev = nullptr;
+        if (std::any_of(planes.begin(), planes.end(), [](const HostPlane& h) { return (bool)h; })) TOPO_TRY(extra(dev));
+        for (const HostPlane& h : planes) pages.prefault(h.host, h.bytes(ny, nx));
+        return TOPO_AMD_OK;
+    }
+    float* at(float* p, int r0) const { return shift(p, r0, nx); }
+    template <class Compute>
+    int run(int below, bool one_chunk, Compute&& compute);
+};
+
+// ---- upload || kernels || download in row chunks (VERDICT r04 item 5) -------------------------------------------------------
+// A host-buffer call used to be three serial steps - 18.7 ms up, 1.3 ms of kernels, 19.9 ms down for TPI 67 px on 16384^2 -
+// over a link that carries both directions at once (48.6 GB/s each way against 57 one way, profiles/r01_host_path.txt).  Row
+// blocks give the single block's bits, so the call is cut into row chunks: the calling thread uploads chunk k on one
+// stream and, as soon as the rows a chunk's outputs depend on are on the device, enqueues its kernels (on the block view
+// "the rows uploaded so far") on the compute stream; a second host thread downloads the output rows of every finished
+// chunk on a third stream (its own thread because copies to and from pageable memory block the caller).
+// TOPO_AMD_HOST_PIPELINE=0: one chunk (the old order).  TOPO_AMD_HOST_CHUNK_MB: size of a chunk of the DEM (default 64).
+// TOPO_AMD_HOST_DOWNLOADS=thread / inline: who issues the downloads (default: by the arrays, below).  All three are read at
+// every call (a getenv each), so a test can walk through them in one process.
+// compute(view, r0): enqueue the kernels that write the output rows of the block `view` - rows [r0, r0 + view.out_rows) of
+// every plane - reading the rows of d_in that are uploaded so far (the whole of view).  below: rows of the DEM beneath an
+// output row that it depends on.  A source that is not float32-as-stored goes chunk by chunk into a raw device plane and is
+// decoded into d_in on the stream of the copy, in front of the event the kernels wait for.
+// one_chunk: the call is not cut, whatever TOPO_AMD_HOST_* say.
 template <class Compute>
-int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, int below, bool upload, bool one_chunk,
-                  std::vector<HostPlane> outs, Compute&& compute) {
+int HostCall::run(int below, bool one_chunk, Compute&& compute_view) {
     Context& c = ctx();
+    const bool upload = !uploaded;
+    uploaded = true;
+    auto compute = [&](int view_rows, int r0, int rows) { return compute_view(Block{d_in, view_rows, 0, ny, nx, r0, rows}, r0); };
     char* d_raw = nullptr;
-    if (upload) TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    if (upload) TOPO_TRY(raw_plane(pool, src, ny, nx, &d_raw));
     // packed result planes: their device planes (behind every plane a float32 call takes), one pair of counters each
     EncodeCounts counts;
     for (HostPlane& o : outs) {
@@ -280,7 +351,7 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
         if (o.pool && *o.pool) {
             o.dev = *o.pool;
         } else {
-            TOPO_TRY(run.alloc(&o.dev, (size_t)ny * nx * (o.pool ? 2 : o.elem)));
+            TOPO_TRY(pool.alloc(&o.dev, samples() * (o.pool ? 2 : o.elem)));
             if (o.pool) *o.pool = o.dev;
         }
     }
@@ -304,20 +375,18 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
             if (outs[q].packed() && outs[q].report) counts.store(q, outs[q].report);
         return TOPO_AMD_OK;
     };
-    const int chunk = one_chunk ? ny : pipeline_chunk_rows(ny, nx);
-    const std::vector<int> cut = chunk >= ny ? std::vector<int>{0, ny} : pipeline_cuts(ny, chunk);
+    const std::vector<int> cut = row_cuts(ny, nx, one_chunk);
     const int nchunks = (int)cut.size() - 1;
-    t_host_chunks = std::max(t_host_chunks, nchunks < 3 ? 1 : nchunks);  // (a multi-scale call: the most any of its scales ran in)
-    if (nchunks < 3) {
+    t_host_chunks = std::max(t_host_chunks, nchunks);  // (a multi-scale call: the most any of its scales ran in)
+    if (nchunks == 1) {
         if (upload) TOPO_HIP(enqueue_rows(src, d_raw, d_in, 0, ny, nx, c.compute));
         const int rc = compute(ny, 0, ny);
         if (rc != TOPO_AMD_OK && rc != TOPO_AMD_EEMPTY) return rc;
         TOPO_TRY(encode_rows(0, ny));
-        run.ready();
+        pages.ready();
         for (const HostPlane& o : outs)
-            if (o.host) TOPO_HIP(hipMemcpyAsync(o.host, o.dev, (size_t)ny * nx * o.elem, hipMemcpyDeviceToHost, c.compute));
-        if (!one_chunk) TOPO_HIP(hipStreamSynchronize(c.compute));  // (the valley calls synchronise once, behind the counters' copy)
-        TOPO_TRY(finish());
+            if (o.host) TOPO_HIP(hipMemcpyAsync(o.host, o.dev, o.bytes(ny, nx), hipMemcpyDeviceToHost, c.compute));
+        TOPO_TRY(finish());  // (one synchronisation, behind the counters' copy)
         return rc;
     }
     TOPO_TRY(copy_streams(2 * nchunks));
@@ -359,11 +428,11 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
     int down_rc = TOPO_AMD_OK;
     std::string down_error;
     const int device = c.device;
-    if (inline_downloads) run.ready();
+    if (inline_downloads) pages.ready();
     std::thread downloader([&] {
         if (inline_downloads) return;
         (void)hipSetDevice(device);
-        run.ready();  // the result arrays have their pages
+        pages.ready();  // the result arrays have their pages
         for (int j = 0; j < nchunks; ++j) {
             {
                 std::unique_lock<std::mutex> lock(mu);
@@ -455,7 +524,7 @@ int run_pipelined(HostRun& run, const Source& src, float* d_in, int ny, int nx, 
 }  // namespace
 
 void prefault_pages(void* host, size_t bytes) {
-    HostRun pages(false);
+    PageToucher pages;
     pages.prefault(host, bytes);
 }
 
@@ -492,29 +561,18 @@ int topo_amd_tpi_std_packed(const topo_amd_raster* raster, int ny, int nx, int s
                             topo_amd_plane* std_plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "tpi_std", &src));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std: bad DEM");
-    OutPlane tpi_out, std_out;
-    TOPO_TRY(make_out(tpi_plane, "tpi_std", &tpi_out));
-    TOPO_TRY(make_out(std_plane, "tpi_std", &std_out));
-    TOPO_REQUIRE(tpi_out || std_out, "tpi_std: both outputs are NULL");
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_source(src, ny, nx));  // the raster class from the caller's array: no launch, no synchronisation
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "tpi_std"));
+    float *d_tpi, *d_std;
+    TOPO_TRY(call.plane(tpi_plane, &d_tpi));
+    TOPO_TRY(call.plane(std_plane, &d_std));
+    TOPO_REQUIRE(d_tpi || d_std, "tpi_std: both outputs are NULL");
+    ClassScope cls(scan_source(call.src, ny, nx));  // the raster class from the caller's array: no launch, no synchronisation
     int above = 0, below = 0;
     TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)size, sigma, &above, &below));
-    HostRun run;
-    void *d_in = nullptr, *d_tpi = nullptr, *d_std = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    if (tpi_out) TOPO_TRY(run.alloc(&d_tpi, bytes));
-    if (std_out) TOPO_TRY(run.alloc(&d_std, bytes));
-    run.prefault(tpi_out.host, tpi_out.bytes(ny, nx));
-    run.prefault(std_out.host, std_out.bytes(ny, nx));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {tpi_out.on((float*)d_tpi), std_out.on((float*)d_std)},
-                         [&](int view_rows, int r0, int rows) {
-                             Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
-                             return tpi_std_block(b, size, sigma, shift((float*)d_tpi, r0, nx), shift((float*)d_std, r0, nx));
-                         });
+    return call.run(below, kRowChunks, [&](const Block& view, int r0) {
+        return tpi_std_block(view, size, sigma, call.at(d_tpi, r0), call.at(d_std, r0));
+    });
 }
 
 // the same pipeline over the valid-sample kernel (disc_valid.hip): a declared nodata is NaN behind the decode, hence missing
@@ -522,34 +580,23 @@ int topo_amd_tpi_std_valid_packed(const topo_amd_raster* raster, int ny, int nx,
                                   topo_amd_plane* std_plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "tpi_std_valid", &src));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std_valid: bad DEM");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "tpi_std_valid"));
     TOPO_REQUIRE(size >= 1 && min_count >= 1, "tpi_std_valid: size %d, min_count %d (both at least 1)", size, min_count);
-    OutPlane tpi_out, std_out;
-    TOPO_TRY(make_out(tpi_plane, "tpi_std_valid", &tpi_out));
-    TOPO_TRY(make_out(std_plane, "tpi_std_valid", &std_out));
-    TOPO_REQUIRE(tpi_out || std_out, "tpi_std_valid: both outputs are NULL");
+    float *d_tpi, *d_std;
+    TOPO_TRY(call.plane(tpi_plane, &d_tpi));
+    TOPO_TRY(call.plane(std_plane, &d_std));
+    TOPO_REQUIRE(d_tpi || d_std, "tpi_std_valid: both outputs are NULL");
     if (size > kDiscValidMaxSize) {
         set_error("tpi_std_valid: disc size %d; the valid-sample kernel covers 1 ... %d", size, kDiscValidMaxSize);
         return TOPO_AMD_EUNSUP;
     }
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
     int above = 0, below = 0;
     TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)size, 0.0, &above, &below));
-    HostRun run;
-    void *d_in = nullptr, *d_tpi = nullptr, *d_std = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    if (tpi_out) TOPO_TRY(run.alloc(&d_tpi, bytes));
-    if (std_out) TOPO_TRY(run.alloc(&d_std, bytes));
-    run.prefault(tpi_out.host, tpi_out.bytes(ny, nx));
-    run.prefault(std_out.host, std_out.bytes(ny, nx));
     TOPO_TRY(disc_valid_begin());  // one flag word for the launches of every row chunk
-    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {tpi_out.on((float*)d_tpi), std_out.on((float*)d_std)},
-                         [&](int view_rows, int r0, int rows) {
-                             Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
-                             return tpi_std_valid_block(b, size, min_count, shift((float*)d_tpi, r0, nx), shift((float*)d_std, r0, nx));
-                         });
+    return call.run(below, kRowChunks, [&](const Block& view, int r0) {
+        return tpi_std_valid_block(view, size, min_count, call.at(d_tpi, r0), call.at(d_std, r0));
+    });
 }
 
 int topo_amd_tpi_std_valid_raw(const topo_amd_raster* raster, int ny, int nx, int size, int min_count, float* tpi_out,
@@ -562,47 +609,35 @@ int topo_amd_tpi_std_multi_packed(const topo_amd_raster* raster, int ny, int nx,
                                   const double* sigmas, topo_amd_plane* tpi_planes, topo_amd_plane* std_planes) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "tpi_std_multi", &src));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1, "tpi_std_multi: bad DEM");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "tpi_std_multi"));
     TOPO_REQUIRE(n_scales >= 1 && sizes, "tpi_std_multi: no scales");
     TOPO_REQUIRE(tpi_planes || std_planes, "tpi_std_multi: both output lists are NULL");
-    std::vector<OutPlane> tpi_outs(n_scales), std_outs(n_scales);
+    std::vector<HostPlane> tpi_outs(n_scales), std_outs(n_scales);
     for (int k = 0; k < n_scales; ++k) {
-        TOPO_TRY(make_out(tpi_planes ? tpi_planes + k : nullptr, "tpi_std_multi", &tpi_outs[k]));
-        TOPO_TRY(make_out(std_planes ? std_planes + k : nullptr, "tpi_std_multi", &std_outs[k]));
+        TOPO_TRY(make_plane(tpi_planes ? tpi_planes + k : nullptr, "tpi_std_multi", &tpi_outs[k]));
+        TOPO_TRY(make_plane(std_planes ? std_planes + k : nullptr, "tpi_std_multi", &std_outs[k]));
     }
-    bool any_tpi = false, any_std = false;
-    for (int k = 0; k < n_scales; ++k) {
-        const bool t = (bool)tpi_outs[k], s = (bool)std_outs[k];
-        TOPO_REQUIRE(t || s, "tpi_std_multi: scale %d has no output plane", k);
-        any_tpi |= t;
-        any_std |= s;
-    }
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_source(src, ny, nx));
-    HostRun run;
-    void *d_in = nullptr, *d_tpi = nullptr, *d_std = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    if (any_tpi) TOPO_TRY(run.alloc(&d_tpi, bytes));
-    if (any_std) TOPO_TRY(run.alloc(&d_std, bytes));
-    for (int k = 0; k < n_scales; ++k) {
-        run.prefault(tpi_outs[k].host, tpi_outs[k].bytes(ny, nx));
-        run.prefault(std_outs[k].host, std_outs[k].bytes(ny, nx));
-    }
-    void *p_tpi = nullptr, *p_std = nullptr;  // the packed device planes, one of each kind for all the scales
+    for (int k = 0; k < n_scales; ++k) TOPO_REQUIRE(tpi_outs[k] || std_outs[k], "tpi_std_multi: scale %d has no output plane", k);
+    ClassScope cls(scan_source(call.src, ny, nx));
+    float *d_tpi, *d_std;  // one device plane of each kind, and (p_*) one packed device plane, for all the scales
+    TOPO_TRY(call.shared(tpi_outs, &d_tpi));
+    TOPO_TRY(call.shared(std_outs, &d_std));
+    void *p_tpi = nullptr, *p_std = nullptr;
     // scale 0 rides on the upload; every scale overlaps its kernels with its own downloads (the two device planes are
     // reused, so a scale starts when the one before it is down)
     for (int k = 0; k < n_scales; ++k) {
-        float* t = tpi_outs[k] ? (float*)d_tpi : nullptr;
-        float* sd = std_outs[k] ? (float*)d_std : nullptr;
+        float* t = tpi_outs[k] ? d_tpi : nullptr;
+        float* sd = std_outs[k] ? d_std : nullptr;
+        const double sigma = sigmas ? sigmas[k] : 0.0;
         int above = 0, below = 0;
-        TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)sizes[k], sigmas ? sigmas[k] : 0.0, &above, &below));
-        TOPO_TRY(run_pipelined(run, src, (float*)d_in, ny, nx, below, k == 0, kRowChunks,
-                               {tpi_outs[k].on(t, &p_tpi), std_outs[k].on(sd, &p_std)}, [&](int view_rows, int r0, int rows) {
-                                   Block b{(const float*)d_in, view_rows, 0, ny, nx, r0, rows};
-                                   return tpi_std_block(b, sizes[k], sigmas ? sigmas[k] : 0.0, shift(t, r0, nx), shift(sd, r0, nx));
-                               }));
+        TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_TPI, (double)sizes[k], sigma, &above, &below));
+        call.outs.clear();
+        call.add(tpi_outs[k], t, &p_tpi);
+        call.add(std_outs[k], sd, &p_std);
+        TOPO_TRY(call.run(below, kRowChunks, [&](const Block& view, int r0) {
+            return tpi_std_block(view, sizes[k], sigma, call.at(t, r0), call.at(sd, r0));
+        }));
     }
     return TOPO_AMD_OK;
 }
@@ -643,26 +678,18 @@ int topo_amd_gauss_raw(const topo_amd_raster* raster, int ny, int nx, double sig
 int topo_amd_gauss_packed(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, topo_amd_plane* plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "gauss", &src));
-    OutPlane out;
-    TOPO_TRY(make_out(plane, "gauss", &out));
-    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "gauss: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "gauss", "bad arguments"));
+    float* d_out;
+    TOPO_TRY(call.plane(plane, &d_out));
+    TOPO_REQUIRE(d_out, "gauss: bad arguments");
     TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gaussian: negative sigma");
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_source(src, ny, nx));
+    ClassScope cls(scan_source(call.src, ny, nx));
     int above = 0, below = 0;
     TOPO_TRY(topo_amd_halo_rows(TOPO_AMD_DESC_GAUSS, sigma_y, 0.0, &above, &below));
-    HostRun run;
-    void *d_in = nullptr, *d_out = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_out, bytes));
-    run.prefault(out.host, out.bytes(ny, nx));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {out.on((float*)d_out)},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_gaussian_dev((const float*)d_in, view_rows, 0, ny, nx, sigma_y, sigma_x, r0, rows,
-                                                          shift((float*)d_out, r0, nx));
-                         });
+    return call.run(below, kRowChunks, [&](const Block& v, int r0) {
+        return topo_amd_gaussian_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, sigma_y, sigma_x, r0, v.out_rows, call.at(d_out, r0));
+    });
 }
 
 // the valid-sample Gaussian (gauss_valid.hip) through the same pipeline: a declared nodata is NaN behind the decode, hence a
@@ -671,30 +698,19 @@ int topo_amd_gauss_valid_packed(const topo_amd_raster* raster, int ny, int nx, d
                                 int fill, topo_amd_plane* plane, float* weight_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "gauss_valid", &src));
-    OutPlane out, weight;
-    TOPO_TRY(make_out(plane, "gauss_valid", &out));
-    topo_amd_plane w = f32_plane(weight_out);
-    TOPO_TRY(make_out(&w, "gauss_valid", &weight));
-    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "gauss_valid: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "gauss_valid", "bad arguments"));
+    float *d_out, *d_weight;
+    TOPO_TRY(call.plane(plane, &d_out));
+    TOPO_TRY(call.stored(weight_out, &d_weight));
+    TOPO_REQUIRE(d_out, "gauss_valid: bad arguments");
     TOPO_REQUIRE(sigma_y >= 0.0 && sigma_x >= 0.0, "gauss_valid: negative sigma");
     TOPO_REQUIRE(min_weight >= 0.0 && min_weight <= 1.0, "gauss_valid: min_weight %g outside [0, 1]", min_weight);
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
     const int below = (int)std::min(4.0 * sigma_y + 0.5, kGaussValidMaxRadius + 1.0);  // the radius: all the ghost rows it wants
-    HostRun run;
-    void *d_in = nullptr, *d_out = nullptr, *d_weight = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_out, bytes));
-    if (weight) TOPO_TRY(run.alloc(&d_weight, bytes));
-    run.prefault(out.host, out.bytes(ny, nx));
-    run.prefault(weight.host, weight.bytes(ny, nx));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, below, true, kRowChunks, {out.on((float*)d_out), weight.on((float*)d_weight)},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_gaussian_valid_dev((const float*)d_in, view_rows, 0, ny, nx, sigma_y, sigma_x, min_weight,
-                                                                fill, r0, rows, shift((float*)d_out, r0, nx),
-                                                                shift((float*)d_weight, r0, nx));
-                         });
+    return call.run(below, kRowChunks, [&](const Block& v, int r0) {
+        return topo_amd_gaussian_valid_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, sigma_y, sigma_x, min_weight, fill, r0, v.out_rows,
+                                           call.at(d_out, r0), call.at(d_weight, r0));
+    });
 }
 
 int topo_amd_gauss_valid_raw(const topo_amd_raster* raster, int ny, int nx, double sigma_y, double sigma_x, double min_weight,
@@ -706,46 +722,33 @@ int topo_amd_gauss_valid_raw(const topo_amd_raster* raster, int ny, int nx, doub
 int topo_amd_sobel_raw(const topo_amd_raster* raster, int ny, int nx, float* dx_out, float* dy_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "sobel", &src));
-    TOPO_REQUIRE(dx_out && dy_out && ny >= 1 && nx >= 1, "sobel: bad arguments");
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    HostRun run;
-    void *d_in = nullptr, *d_dx = nullptr, *d_dy = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_dx, bytes));
-    TOPO_TRY(run.alloc(&d_dy, bytes));
-    run.prefault(dx_out, bytes);
-    run.prefault(dy_out, bytes);
-    return run_pipelined(run, src, (float*)d_in, ny, nx, 1, true, kRowChunks, {{dx_out, (float*)d_dx}, {dy_out, (float*)d_dy}},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_sobel_dev((const float*)d_in, view_rows, 0, ny, nx, r0, rows, shift((float*)d_dx, r0, nx),
-                                                       shift((float*)d_dy, r0, nx));
-                         });
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "sobel", "bad arguments"));
+    TOPO_REQUIRE(dx_out && dy_out, "sobel: bad arguments");
+    float *d_dx, *d_dy;
+    TOPO_TRY(call.stored(dx_out, &d_dx));
+    TOPO_TRY(call.stored(dy_out, &d_dy));
+    return call.run(1, kRowChunks, [&](const Block& v, int r0) {
+        return topo_amd_sobel_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, r0, v.out_rows, call.at(d_dx, r0), call.at(d_dy, r0));
+    });
 }
 
 int topo_amd_fill_na_raw(const topo_amd_raster* raster, int ny, int nx, const double* x_coords, double min_elevation, float* out,
                          uint8_t* missing_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "fill_na", &src));
-    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "fill_na: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "fill_na", "bad arguments"));
+    TOPO_REQUIRE(out, "fill_na: bad arguments");
     bool ascending = true;
     TOPO_TRY(check_fill_coords(x_coords, nx, &ascending));  // (before anything moves)
-    const size_t bytes = (size_t)ny * nx * sizeof(float), mask_bytes = (size_t)ny * nx;
-    HostRun run;
-    void *d_plane = nullptr, *d_miss = nullptr;
-    TOPO_TRY(run.alloc(&d_plane, bytes));  // filled in place on the device
-    if (missing_out) TOPO_TRY(run.alloc(&d_miss, mask_bytes));
-    run.prefault(out, bytes);
-    run.prefault(missing_out, mask_bytes);
-    return run_pipelined(run, src, (float*)d_plane, ny, nx, 0, true, kRowChunks, {{out, d_plane}, {missing_out, d_miss, 1}},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_fill_na_dev((const float*)d_plane, view_rows, 0, ny, nx, x_coords, min_elevation, r0, rows,
-                                                         shift((float*)d_plane, r0, nx),
-                                                         d_miss ? (uint8_t*)d_miss + (size_t)r0 * nx : nullptr);
-                         });
+    uint8_t* d_miss;
+    call.in_place(out, call.d_in);  // filled in place on the device
+    TOPO_TRY(call.stored(missing_out, &d_miss));
+    return call.run(0, kRowChunks, [&](const Block& v, int r0) {
+        return topo_amd_fill_na_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, x_coords, min_elevation, r0, v.out_rows,
+                                    call.at(call.d_in, r0), d_miss ? d_miss + (size_t)r0 * nx : nullptr);
+    });
 }
 
 int topo_amd_gradient_raw(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio,
@@ -760,43 +763,32 @@ int topo_amd_gradient_packed(const topo_amd_raster* raster, int ny, int nx, doub
                              topo_amd_plane* slope_out, topo_amd_plane* aspect_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "gradient", &src));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1, "gradient: bad DEM");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "gradient"));
     topo_amd_plane* planes[4] = {dx_out, dy_out, slope_out, aspect_out};
-    OutPlane host_out[4];
-    for (int k = 0; k < 4; ++k) TOPO_TRY(make_out(planes[k], "gradient", &host_out[k]));
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    ClassScope cls(scan_source(src, ny, nx));
-    HostRun run;
-    void *d_in = nullptr, *d_o[4] = {nullptr, nullptr, nullptr, nullptr};
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    for (int k = 0; k < 4; ++k)
-        if (host_out[k]) TOPO_TRY(run.alloc(&d_o[k], bytes));
-    for (int k = 0; k < 4; ++k) run.prefault(host_out[k].host, host_out[k].bytes(ny, nx));
+    float* d_o[4];
+    for (int k = 0; k < 4; ++k) TOPO_TRY(call.plane(planes[k], &d_o[k]));
+    ClassScope cls(scan_source(call.src, ny, nx));
     const void *rx = res_x, *ry = res_y;
-    if (res_mode == TOPO_AMD_RES_2D) {
+    if (res_mode == TOPO_AMD_RES_2D) {  // the call's extras: the two resolution planes on the device
         TOPO_REQUIRE(res_x && res_y, "gradient: resolution arrays are NULL");
-        void *d_rx = nullptr, *d_ry = nullptr;
-        TOPO_TRY(run.alloc(&d_rx, bytes));
-        TOPO_TRY(run.alloc(&d_ry, bytes));
-        TOPO_HIP(hipMemcpyAsync(d_rx, res_x, bytes, hipMemcpyHostToDevice, ctx().compute));
-        TOPO_HIP(hipMemcpyAsync(d_ry, res_y, bytes, hipMemcpyHostToDevice, ctx().compute));
+        float *d_rx, *d_ry;
+        TOPO_TRY(call.extra(&d_rx));
+        TOPO_TRY(call.extra(&d_ry));
+        TOPO_HIP(hipMemcpyAsync(d_rx, res_x, call.samples() * sizeof(float), hipMemcpyHostToDevice, ctx().compute));
+        TOPO_HIP(hipMemcpyAsync(d_ry, res_y, call.samples() * sizeof(float), hipMemcpyHostToDevice, ctx().compute));
         rx = d_rx;
         ry = d_ry;
     }
     const int h = gradient_ghost_rows(sigma, sig_ratio, true);
-    std::vector<HostPlane> outs;
-    for (int k = 0; k < 4; ++k) outs.push_back(host_out[k].on((float*)d_o[k]));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, h, true, kRowChunks, outs, [&](int view_rows, int r0, int rows) {
+    return call.run(h, kRowChunks, [&](const Block& v, int r0) {
         const void *cx = rx, *cy = ry;
         if (res_mode == TOPO_AMD_RES_2D) {  // [out_rows x nx], aligned with the output rows
             cx = (const float*)rx + (size_t)r0 * nx;
             cy = (const float*)ry + (size_t)r0 * nx;
         }
-        return topo_amd_gradient_dev((const float*)d_in, view_rows, 0, ny, nx, sigma, sig_ratio, res_mode, cx, cy, r0, rows,
-                                     shift((float*)d_o[0], r0, nx), shift((float*)d_o[1], r0, nx), shift((float*)d_o[2], r0, nx),
-                                     shift((float*)d_o[3], r0, nx));
+        return topo_amd_gradient_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, sigma, sig_ratio, res_mode, cx, cy, r0, v.out_rows,
+                                     call.at(d_o[0], r0), call.at(d_o[1], r0), call.at(d_o[2], r0), call.at(d_o[3], r0));
     });
 }
 
@@ -810,27 +802,20 @@ int topo_amd_sx_packed(const topo_amd_raster* raster, int ny, int nx, const int3
                        int n_off, int window, double height, topo_amd_plane* plane) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "sx", &src));
-    OutPlane out;
-    TOPO_TRY(make_out(plane, "sx", &out));
-    TOPO_REQUIRE(out && ny >= 1 && nx >= 1, "sx: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "sx", "bad arguments"));
+    float* d_out;
+    TOPO_TRY(call.plane(plane, &d_out));
+    TOPO_REQUIRE(d_out, "sx: bad arguments");
     // (no ray pixel at all: the tables may be NULL; the plane is zero-filled and the call answers TOPO_AMD_EEMPTY, like
     // a sector whose pixels are all NaN)
     TOPO_REQUIRE(n_off >= 0 && (n_off == 0 || (dj && di && dist)), "sx: NULL argument");
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
     int up = 0, down = 0;
     sx_reach(dj, dist, 0, n_off, &up, &down);
-    HostRun run;
-    void *d_in = nullptr, *d_out = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_out, bytes));
-    run.prefault(out.host, out.bytes(ny, nx));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, down, true, kRowChunks, {out.on((float*)d_out)},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_sx_dev((const float*)d_in, view_rows, 0, ny, nx, dj, di, dist, n_off, window, height, r0, rows,
-                                                    shift((float*)d_out, r0, nx));
-                         });
+    return call.run(down, kRowChunks, [&](const Block& v, int r0) {
+        return topo_amd_sx_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, dj, di, dist, n_off, window, height, r0, v.out_rows,
+                               call.at(d_out, r0));
+    });
 }
 
 int topo_amd_sx_multi_raw(const topo_amd_raster* raster, int ny, int nx, int n_az, const int32_t* first,
@@ -846,30 +831,20 @@ int topo_amd_sx_multi_packed(const topo_amd_raster* raster, int ny, int nx, int 
                              topo_amd_plane* out_planes) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "sx_multi", &src));
-    TOPO_REQUIRE(out_planes && n_az >= 1 && ny >= 1 && nx >= 1, "sx_multi: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "sx_multi", "bad arguments"));
+    TOPO_REQUIRE(out_planes && n_az >= 1, "sx_multi: bad arguments");
     TOPO_REQUIRE(first && dj && di && dist && window, "sx_multi: NULL argument");
-    std::vector<OutPlane> outs(n_az);
+    std::vector<float*> d_out(n_az, nullptr), moved(n_az);
     for (int k = 0; k < n_az; ++k) {
-        TOPO_TRY(make_out(out_planes + k, "sx_multi", &outs[k]));
-        TOPO_REQUIRE(outs[k], "sx_multi: NULL output plane %d", k);
+        TOPO_TRY(call.plane(out_planes + k, &d_out[k]));
+        TOPO_REQUIRE(d_out[k], "sx_multi: NULL output plane %d", k);
     }
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    HostRun run;
-    void* d_in = nullptr;
-    std::vector<float*> d_out(n_az, nullptr);
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    for (int k = 0; k < n_az; ++k) TOPO_TRY(run.alloc((void**)&d_out[k], bytes));
-    for (int k = 0; k < n_az; ++k) run.prefault(outs[k].host, outs[k].bytes(ny, nx));
     int up = 0, down = 0;
     sx_reach(dj, dist, first[0], first[n_az], &up, &down);
-    std::vector<HostPlane> planes;
-    for (int k = 0; k < n_az; ++k) planes.push_back(outs[k].on(d_out[k]));
-    std::vector<float*> moved(n_az);
-    return run_pipelined(run, src, (float*)d_in, ny, nx, down, true, kRowChunks, planes, [&](int view_rows, int r0, int rows) {
-        for (int k = 0; k < n_az; ++k) moved[k] = shift(d_out[k], r0, nx);
-        return topo_amd_sx_multi_dev((const float*)d_in, view_rows, 0, ny, nx, n_az, first, dj, di, dist, window, height, r0, rows,
+    return call.run(down, kRowChunks, [&](const Block& v, int r0) {
+        for (int k = 0; k < n_az; ++k) moved[k] = call.at(d_out[k], r0);
+        return topo_amd_sx_multi_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, n_az, first, dj, di, dist, window, height, r0, v.out_rows,
                                      moved.data());  // (EEMPTY: every plane was written)
     });
 }
@@ -879,25 +854,18 @@ int topo_amd_valley_ridge_raw(const topo_amd_raster* raster, int ny, int nx, con
                               float* norm_out, float* dir_out) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "valley_ridge", &src));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1 && norm_out && dir_out, "valley_ridge: bad arguments");
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    HostRun run;
-    void *d_in = nullptr, *d_norm = nullptr, *d_dir = nullptr;
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_norm, bytes));
-    TOPO_TRY(run.alloc(&d_dir, bytes));
-    run.prefault(norm_out, bytes);
-    run.prefault(dir_out, bytes);
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "valley_ridge", "bad arguments"));
+    TOPO_REQUIRE(norm_out && dir_out, "valley_ridge: bad arguments");
+    float *d_norm, *d_dir;
+    TOPO_TRY(call.stored(norm_out, &d_norm));
+    TOPO_TRY(call.stored(dir_out, &d_dir));
     // (not pipelined: half a second of kernels per 20 ms of copies at full size, and the FFT route of the large kernels is
     // not cut-invariant)
-    return run_pipelined(run, src, (float*)d_in, ny, nx, 0, true, kOneChunk, {{norm_out, d_norm}, {dir_out, d_dir}},
-                         [&](int view_rows, int r0, int rows) {
-                             return topo_amd_valley_ridge_dev((const float*)d_in, view_rows, 0, ny, nx, taps, ksize, angles, n_angles,
-                                                              n_planes, mean, stdev, r0, rows, shift((float*)d_norm, r0, nx),
-                                                              shift((float*)d_dir, r0, nx));
-                         });
+    return call.run(0, kOneChunk, [&](const Block& v, int r0) {
+        return topo_amd_valley_ridge_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, taps, ksize, angles, n_angles, n_planes, mean, stdev, r0,
+                                         v.out_rows, call.at(d_norm, r0), call.at(d_dir, r0));
+    });
 }
 
 // The standardised, optionally smoothed and optionally packed index of a host raster in one call: upload and decode, the
@@ -908,32 +876,23 @@ int topo_amd_valley_ridge_packed(const topo_amd_raster* raster, int ny, int nx, 
                                  topo_amd_plane* norm_plane, topo_amd_plane* dir_plane, float moments_out[2]) {
     TOPO_ENTER();
     TOPO_TRY(require_ready());
-    Source src;
-    TOPO_TRY(make_source(raster, "valley_ridge", &src));
-    OutPlane outs[2];
-    TOPO_TRY(make_out(norm_plane, "valley_ridge", &outs[0]));
-    TOPO_TRY(make_out(dir_plane, "valley_ridge", &outs[1]));
-    TOPO_REQUIRE(ny >= 1 && nx >= 1 && outs[0] && outs[1], "valley_ridge: bad arguments");
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "valley_ridge", "bad arguments"));
+    float *d_norm, *d_dir, *d_smooth = nullptr;
+    TOPO_TRY(call.plane(norm_plane, &d_norm));
+    TOPO_TRY(call.plane(dir_plane, &d_dir));
+    TOPO_REQUIRE(d_norm && d_dir, "valley_ridge: bad arguments");
     TOPO_REQUIRE(sigma >= 0.0, "valley_ridge: sigma %g", sigma);
-    const size_t bytes = (size_t)ny * nx * sizeof(float);
-    HostRun run;
-    void *d_in = nullptr, *d_smooth = nullptr, *d_res[2] = {nullptr, nullptr};
-    TOPO_TRY(run.alloc(&d_in, bytes));
-    TOPO_TRY(run.alloc(&d_res[0], bytes));
-    TOPO_TRY(run.alloc(&d_res[1], bytes));
-    if (sigma > 0.0) TOPO_TRY(run.alloc(&d_smooth, bytes));
-    for (int q = 0; q < 2; ++q) run.prefault(outs[q].host, outs[q].bytes(ny, nx));
-    return run_pipelined(run, src, (float*)d_in, ny, nx, 0, true, kOneChunk, {outs[0].on((float*)d_res[0]), outs[1].on((float*)d_res[1])},
-                         [&](int, int, int) {  // (one chunk: the whole raster)
-                             const float* field = (const float*)d_in;
-                             if (sigma > 0.0) {
-                                 ClassScope cls(scan_source(src, ny, nx));  // the smoothing kernels topo_amd_gauss_raw takes for this raster
-                                 TOPO_TRY(topo_amd_gaussian_dev(field, ny, 0, ny, nx, sigma, sigma, 0, ny, (float*)d_smooth));
-                                 field = (const float*)d_smooth;
-                             }
-                             return topo_amd_valley_ridge_std_dev(field, ny, nx, taps, ksize, angles, n_angles, n_planes, chunk,
-                                                                  (float*)d_res[0], (float*)d_res[1], moments_out);
-                         });
+    if (sigma > 0.0) TOPO_TRY(call.extra(&d_smooth));  // the call's extra: the smoothed plane
+    return call.run(0, kOneChunk, [&](const Block& v, int) {  // (one chunk: the whole raster)
+        const float* field = v.in;
+        if (sigma > 0.0) {
+            ClassScope cls(scan_source(call.src, ny, nx));  // the smoothing kernels topo_amd_gauss_raw takes for this raster
+            TOPO_TRY(topo_amd_gaussian_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, sigma, sigma, v.out_row0, v.out_rows, d_smooth));
+            field = d_smooth;
+        }
+        return topo_amd_valley_ridge_std_dev(field, ny, nx, taps, ksize, angles, n_angles, n_planes, chunk, d_norm, d_dir, moments_out);
+    });
 }
 
 int topo_amd_valley_ridge_std_raw(const topo_amd_raster* raster, int ny, int nx, const float* taps, const int32_t* ksize,
@@ -1095,13 +1054,12 @@ int topo_amd_upload_raw(const topo_amd_raster* raster, int ny, int nx, float* ou
     TOPO_REQUIRE(out_dev && ny >= 1 && nx >= 1, "upload_raw: bad arguments");
     Context& c = ctx();
     dem_memo_forget(out_dev, (size_t)ny * nx * sizeof(float));
-    HostRun run(false);
+    PlanePool pool;
     char* d_raw = nullptr;
-    TOPO_TRY(raw_plane(run, src, ny, nx, &d_raw));
+    TOPO_TRY(raw_plane(pool, src, ny, nx, &d_raw));
     // the copies on the upload stream, each chunk's decode on the compute stream behind its copy: chunk k is decoded while
     // chunk k + 1 crosses the link (float32 as stored: nothing to decode, one copy)
-    const int chunk = src.as_stored ? ny : pipeline_chunk_rows(ny, nx);
-    const std::vector<int> cut = chunk >= ny ? std::vector<int>{0, ny} : pipeline_cuts(ny, chunk);
+    const std::vector<int> cut = row_cuts(ny, nx, src.as_stored);
     const int nchunks = (int)cut.size() - 1;
     if (nchunks == 1) {
         TOPO_HIP(enqueue_rows(src, d_raw, out_dev, 0, ny, nx, c.compute));

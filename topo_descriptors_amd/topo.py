@@ -47,8 +47,8 @@ def _values(v):
 
 
 def _source(values):
-    """``(keep, by-reference Raster, shape)`` of an ndarray or ``PackedDem`` for the ``*_raw`` entry points: supported dtypes
-    go to the GPU as stored (``_lib.as_source``); ``keep`` holds the memory the struct points into."""
+    """``(keep, by-reference Raster, shape)`` of an ndarray or ``PackedDem`` for the host-buffer entry points: supported
+    dtypes go to the GPU as stored (``_lib.as_source``); ``keep`` holds the memory the struct points into."""
     keep, raster = _lib.source_of(values)
     return keep, C.byref(raster), keep.shape
 
@@ -57,14 +57,19 @@ def _plane(shape):
     return np.empty(shape, dtype=np.float32)
 
 
-def _packed_tpi_std(values, size, sigma, packs, want):
-    """``topo_amd_tpi_std_packed``: the planes of ``want`` (tpi, std) with the packings ``packs``; an unpacked STD plane is
+def _tpi_std(values, size, sigma, packs, want, skipna=False, min_count=1):
+    """The planes of ``want`` (tpi, std) with the packings ``packs`` (``None``: float32) from ``topo_amd_tpi_std_packed`` or,
+    with ``skipna``, from ``topo_amd_tpi_std_valid_packed`` (over the valid samples of the disc); an unpacked STD plane is
     widened to float64 as :func:`std` does."""
     keep, src, shape = _source(values)
     made = [_lib.result_plane(q, shape) if w else None for q, w in zip(packs, want)]
     refs = [C.byref(m[1]) if m else None for m in made]
-    _lib.check(_lib.lib().topo_amd_tpi_std_packed(src, shape[0], shape[1], int(size), _sigma_arg(sigma), *refs),
-               "topo_amd_tpi_std_packed")
+    if skipna:
+        _lib.check(_lib.lib().topo_amd_tpi_std_valid_packed(src, shape[0], shape[1], int(size), int(min_count), *refs),
+                   "topo_amd_tpi_std_valid_packed")
+    else:
+        _lib.check(_lib.lib().topo_amd_tpi_std_packed(src, shape[0], shape[1], int(size), _sigma_arg(sigma), *refs),
+                   "topo_amd_tpi_std_packed")
     out = [_lib.wrap_plane(*m, q) if m else None for m, q in zip(made, packs)]
     if want[1] and packs[1] is None:
         out[1] = out[1].astype(np.float64)
@@ -83,20 +88,6 @@ def _skipna_args(skipna, min_count, sigma, who):
     if int(min_count) != min_count or int(min_count) < 1:
         raise ValueError(f"{who}: min_count {min_count!r} (a whole number of valid samples, at least 1)")
     return int(min_count)
-
-
-def _valid_tpi_std(values, size, min_count, packs, want):
-    """``topo_amd_tpi_std_valid_packed``: the planes of ``want`` (tpi, std) over the valid samples of the disc, with the
-    packings ``packs`` (``None``: float32; an unpacked STD plane is widened to float64 as :func:`std` does)."""
-    keep, src, shape = _source(values)
-    made = [_lib.result_plane(q, shape) if w else None for q, w in zip(packs, want)]
-    refs = [C.byref(m[1]) if m else None for m in made]
-    _lib.check(_lib.lib().topo_amd_tpi_std_valid_packed(src, shape[0], shape[1], int(size), int(min_count), *refs),
-               "topo_amd_tpi_std_valid_packed")
-    out = [_lib.wrap_plane(*m, q) if m else None for m, q in zip(made, packs)]
-    if want[1] and packs[1] is None:
-        out[1] = out[1].astype(np.float64)
-    return out
 
 
 def _check_2d(a, who):
@@ -152,18 +143,8 @@ def tpi(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     min_count = _skipna_args(skipna, min_count, sigma, "tpi")
     values, rewrap = _unwrap(dem)
     _check_2d(values, "tpi")
-    if skipna:
-        packs = _lib.pack_list(pack, ["tpi"]) + [None]
-        out = _valid_tpi_std(values, size, min_count, packs, (True, False))[0]
-        return rewrap(out) if pack is None else out
-    if pack is not None:
-        return _packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi"]) + [None], (True, False))[0]
-    keep, src, shape = _source(values)
-    out = _plane(shape)
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_tpi_raw(src, shape[0], shape[1], int(size),
-                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_tpi_raw")
-    return rewrap(out)
+    out = _tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi"]) + [None], (True, False), skipna, min_count)[0]
+    return rewrap(out) if pack is None else out
 
 
 def std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
@@ -178,16 +159,7 @@ def std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     min_count = _skipna_args(skipna, min_count, sigma, "std")
     values, _ = _unwrap(dem)
     _check_2d(values, "std")
-    if skipna:
-        return _valid_tpi_std(values, size, min_count, [None] + _lib.pack_list(pack, ["std"]), (False, True))[1]
-    if pack is not None:
-        return _packed_tpi_std(values, size, sigma, [None] + _lib.pack_list(pack, ["std"]), (False, True))[1]
-    keep, src, shape = _source(values)
-    out = _plane(shape)
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_std_raw(src, shape[0], shape[1], int(size),
-                                    _sigma_arg(sigma), _lib.ptr(out)), "topo_amd_std_raw")
-    return out.astype(np.float64)
+    return _tpi_std(values, size, sigma, [None] + _lib.pack_list(pack, ["std"]), (False, True), skipna, min_count)[1]
 
 
 def tpi_std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
@@ -198,18 +170,7 @@ def tpi_std(dem, size, sigma=None, pack=None, skipna=False, min_count=1):
     min_count = _skipna_args(skipna, min_count, sigma, "tpi_std")
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std")
-    if skipna:
-        return tuple(_valid_tpi_std(values, size, min_count, _lib.pack_list(pack, ["tpi", "std"]), (True, True)))
-    if pack is not None:
-        return tuple(_packed_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi", "std"]), (True, True)))
-    keep, src, shape = _source(values)
-    t = _plane(shape)
-    s = _plane(shape)
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_tpi_std_raw(src, shape[0], shape[1], int(size),
-                                        _sigma_arg(sigma), _lib.ptr(t), _lib.ptr(s)),
-               "topo_amd_tpi_std_raw")
-    return t, s.astype(np.float64)
+    return tuple(_tpi_std(values, size, sigma, _lib.pack_list(pack, ["tpi", "std"]), (True, True), skipna, min_count))
 
 
 def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True, pack=None):
@@ -219,7 +180,6 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True, pack=No
     for); every plane has the bits of the single call.  ``pack``: one :class:`Packing` for every plane, or a pair / a dict
     with the keys ``tpi`` and ``std`` whose entries are ``None`` (float32), a :class:`Packing` or a sequence with one entry per
     size."""
-    import ctypes as C
     values, _ = _unwrap(dem)
     _check_2d(values, "tpi_std_multi")
     keep, src, shape = _source(values)
@@ -230,46 +190,30 @@ def tpi_std_multi(dem, sizes, sigmas=None, want_tpi=True, want_std=True, pack=No
     else:
         sig = np.array([_sigma_arg(v) for v in np.broadcast_to(np.asarray(sigmas, dtype=object), (n,))],
                        dtype=np.float64)
-    if pack is not None:
-        if isinstance(pack, _lib.Packing):
-            kinds = [pack, pack]
-        else:
-            kinds = [pack.get("tpi"), pack.get("std")] if isinstance(pack, dict) else list(pack)
-        if len(kinds) != 2:
-            raise ValueError("tpi_std_multi: pack is one Packing, or a pair / dict (tpi, std)")
-        names = [str(k) for k in range(n)]
-        lists, arrays = [], []
-        for kind, want in zip(kinds, (want_tpi, want_std)):
-            packs = _lib.pack_list(kind, names)
-            made = [_lib.result_plane(q, shape) for q in packs] if want else None
-            lists.append((packs, made))
-            arrays.append(_lib.plane_array([m[1] for m in made]) if want else None)
-        _lib.check(_lib.lib().topo_amd_tpi_std_multi_packed(src, shape[0], shape[1], n, sizes.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                            sig.ctypes.data_as(C.POINTER(C.c_double)), *arrays),
-                   "topo_amd_tpi_std_multi_packed")
-        out = []
-        for (packs, made), structs, widen in zip(lists, arrays, (False, True)):
-            if made is None:
-                out.append(None)
-                continue
-            planes = [_lib.wrap_plane(m[0], structs[k], q) for k, (m, q) in enumerate(zip(made, packs))]
-            out.append([p.astype(np.float64) if widen and q is None else p for p, q in zip(planes, packs)])
-        return tuple(out)
-    tpis = [_plane(shape) for _ in range(n)] if want_tpi else None
-    stds = [_plane(shape) for _ in range(n)] if want_std else None
-
-    def plane_list(planes):
-        if planes is None:
-            return None
-        return (C.c_void_p * n)(*[p.ctypes.data for p in planes])
-
-    lib = _lib.lib()
-    t_arg, s_arg = plane_list(tpis), plane_list(stds)
-    _lib.check(lib.topo_amd_tpi_std_multi_raw(src, shape[0], shape[1], n,
-                                              sizes.ctypes.data_as(C.POINTER(C.c_int32)),
-                                              sig.ctypes.data_as(C.POINTER(C.c_double)), t_arg, s_arg),
-               "topo_amd_tpi_std_multi_raw")
-    return tpis, ([s.astype(np.float64) for s in stds] if stds is not None else None)
+    if pack is None or isinstance(pack, _lib.Packing):
+        kinds = [pack, pack]
+    else:
+        kinds = [pack.get("tpi"), pack.get("std")] if isinstance(pack, dict) else list(pack)
+    if len(kinds) != 2:
+        raise ValueError("tpi_std_multi: pack is one Packing, or a pair / dict (tpi, std)")
+    names = [str(k) for k in range(n)]
+    lists, arrays = [], []
+    for kind, want in zip(kinds, (want_tpi, want_std)):
+        packs = _lib.pack_list(kind, names)
+        made = [_lib.result_plane(q, shape) for q in packs] if want else None
+        lists.append((packs, made))
+        arrays.append(_lib.plane_array([m[1] for m in made]) if want else None)
+    _lib.check(_lib.lib().topo_amd_tpi_std_multi_packed(src, shape[0], shape[1], n, sizes.ctypes.data_as(_lib._i32p),
+                                                        sig.ctypes.data_as(_lib._f64p), *arrays),
+               "topo_amd_tpi_std_multi_packed")
+    out = []
+    for (packs, made), structs, widen in zip(lists, arrays, (False, True)):
+        if made is None:
+            out.append(None)
+            continue
+        planes = [_lib.wrap_plane(m[0], structs[k], q) for k, (m, q) in enumerate(zip(made, packs))]
+        out.append([p.astype(np.float64) if widen and q is None else p for p, q in zip(planes, packs)])
+    return tuple(out)
 
 
 # ---- Gaussian, Sobel, gradient ------------------------------------------------------------------
@@ -321,28 +265,19 @@ def dem(dem, sigma, pack=None, skipna=False, min_weight=0.0, fill=False, return_
     values, rewrap = _unwrap(dem)
     _check_2d(values, "dem")
     sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (2,))
+    packing, = _lib.pack_list(pack, ["dem"])
     keep, src, shape = _source(values)
+    out, plane = _lib.result_plane(packing, shape)
+    weight = _plane(shape) if return_weight else None
     if skipna:
-        packing, = _lib.pack_list(pack, ["dem"])
-        out, plane = _lib.result_plane(packing, shape)
-        weight = _plane(shape) if return_weight else None
         _lib.check(_lib.lib().topo_amd_gauss_valid_packed(src, shape[0], shape[1], float(sig[0]), float(sig[1]), min_weight,
-                                                          int(bool(fill)), C.byref(plane),
-                                                          _lib.ptr(weight) if return_weight else None),
+                                                          int(bool(fill)), C.byref(plane), _lib.ptr(weight)),
                    "topo_amd_gauss_valid_packed")
-        out = rewrap(out) if packing is None else _lib.wrap_plane(out, plane, packing)  # (a packed plane is not re-wrapped)
-        return (out, weight) if return_weight else out
-    if pack is not None:
-        packing, = _lib.pack_list(pack, ["dem"])
-        out, plane = _lib.result_plane(packing, shape)
+    else:
         _lib.check(_lib.lib().topo_amd_gauss_packed(src, shape[0], shape[1], float(sig[0]), float(sig[1]), C.byref(plane)),
                    "topo_amd_gauss_packed")
-        return _lib.wrap_plane(out, plane, packing)
-    out = _plane(shape)
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_gauss_raw(src, shape[0], shape[1], float(sig[0]),
-                                      float(sig[1]), _lib.ptr(out)), "topo_amd_gauss_raw")
-    return rewrap(out)
+    out = rewrap(out) if packing is None else _lib.wrap_plane(out, plane, packing)  # (a packed plane is not re-wrapped)
+    return (out, weight) if return_weight else out
 
 
 def sobel(dem):
@@ -393,20 +328,13 @@ def gradient(dem, sigma, res_meters, sig_ratio=1, pack=None):
     ``aspect`` (``None`` or a missing key: that plane stays float32); packed planes come back as :class:`PackedPlane`."""
     values, _ = _unwrap(dem)
     _check_2d(values, "gradient")
+    packs = _lib.pack_list(pack, GRADIENT_PLANES)
     keep, src, shape = _source(values)
     mode, rx, ry = _resolution_args(res_meters, shape)
-    if pack is not None:
-        packs = _lib.pack_list(pack, GRADIENT_PLANES)
-        made = [_lib.result_plane(q, shape) for q in packs]
-        _lib.check(_lib.lib().topo_amd_gradient_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), mode, _lib.ptr(rx),
-                                                       _lib.ptr(ry), *[C.byref(m[1]) for m in made]), "topo_amd_gradient_packed")
-        return [_lib.wrap_plane(*m, q) for m, q in zip(made, packs)]
-    outs = [_plane(shape) for _ in range(4)]
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_gradient_raw(src, shape[0], shape[1], float(sigma),
-                                         float(sig_ratio), mode, _lib.ptr(rx), _lib.ptr(ry),
-                                         *[_lib.ptr(o) for o in outs]), "topo_amd_gradient_raw")
-    return outs
+    made = [_lib.result_plane(q, shape) for q in packs]
+    _lib.check(_lib.lib().topo_amd_gradient_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), mode, _lib.ptr(rx),
+                                                   _lib.ptr(ry), *[C.byref(m[1]) for m in made]), "topo_amd_gradient_packed")
+    return [_lib.wrap_plane(*m, q) for m, q in zip(made, packs)]
 
 
 # ---- Sx ---------------------------------------------------------------------------------------------
@@ -457,34 +385,41 @@ def _sx_scan(dem, reach, rows, cols, metres, height, pack=None):
     planes made on the host (nothing but frame, no usable ray pixel) are packed there."""
     dem = _values(dem)
     _check_2d(dem, "_sx_rolling")
-    if pack is not None:
-        packing, = _lib.pack_list(pack, ["sx"])
-        ny, nx = dem.shape
-        if ny <= 2 * reach or nx <= 2 * reach or np.size(metres) == 0 or np.all(np.isnan(metres)):
-            return _lib.encode_host(_sx_scan(np.zeros(dem.shape, np.float32), reach, rows, cols, metres, height), packing)
+    packing, = _lib.pack_list(pack, ["sx"])
+    host = _sx_host_plane(dem.shape, reach, metres)
+    if host is not None:
+        return _sx_result(host, None, packing, dem.dtype)
     metres = np.ascontiguousarray(metres, dtype=np.float64)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
     keep, src, (ny, nx) = _source(dem)
-    out = np.zeros((ny, nx), dtype=np.float32)
-    if ny <= 2 * reach or nx <= 2 * reach:  # nothing but frame
-        return out.astype(dem.dtype, copy=False)
-    if metres.size == 0 or np.all(np.isnan(metres)):
-        # nanmax over an empty / all-NaN set: NaN inside the frame, like numpy
+    out, plane = _lib.result_plane(packing, (ny, nx))
+    _lib.check(_lib.lib().topo_amd_sx_packed(src, ny, nx, rows.ctypes.data_as(_lib._i32p), cols.ctypes.data_as(_lib._i32p),
+                                             metres.ctypes.data_as(_lib._f64p), int(metres.size), int(reach), float(height),
+                                             C.byref(plane)), "topo_amd_sx_packed")
+    return _sx_result(out, plane, packing, dem.dtype)
+
+
+def _sx_host_plane(shape, reach, metres):
+    """The Sx plane of a sector the device has no work for, made on the host (``None``: it has): zeros where the DEM is nothing
+    but the frame of ``reach`` pixels; NaN inside the frame where there is no usable ray pixel (nanmax over an empty / all-NaN
+    set, like numpy)."""
+    ny, nx = shape
+    framed = ny <= 2 * reach or nx <= 2 * reach
+    if not framed and np.size(metres) and not np.all(np.isnan(metres)):
+        return None
+    out = np.zeros(shape, dtype=np.float32)
+    if not framed:
         out[reach : ny - reach, reach : nx - reach] = np.nan
-        return out.astype(dem.dtype, copy=False)
-    if pack is not None:
-        out, plane = _lib.result_plane(packing, (ny, nx))
-        _lib.check(_lib.lib().topo_amd_sx_packed(src, ny, nx, rows.ctypes.data_as(_lib._i32p), cols.ctypes.data_as(_lib._i32p),
-                                                 metres.ctypes.data_as(_lib._f64p), int(metres.size), int(reach), float(height),
-                                                 C.byref(plane)), "topo_amd_sx_packed")
-        return _lib.wrap_plane(out, plane, packing)
-    lib = _lib.lib()
-    _lib.check(lib.topo_amd_sx_raw(src, ny, nx, rows.ctypes.data_as(_lib._i32p),
-                                   cols.ctypes.data_as(_lib._i32p), metres.ctypes.data_as(_lib._f64p),
-                                   int(metres.size), int(reach), float(height), _lib.ptr(out)),
-               "topo_amd_sx_raw")
-    return out.astype(dem.dtype, copy=False)
+    return out
+
+
+def _sx_result(array, plane, packing, dtype):
+    """What an Sx call returns for one plane: unpacked in the DEM's ``dtype``, else a ``PackedPlane`` - of the library's
+    ``plane`` struct, or (``None``: a plane made on the host) packed there."""
+    if packing is None:
+        return array.astype(dtype, copy=False)
+    return _lib.encode_host(array, packing) if plane is None else _lib.wrap_plane(array, plane, packing)
 
 
 def _sx_rolling(dem, distance, blines, height):
@@ -545,47 +480,22 @@ def sx_multi(dem_ds, azimuths, radius, height=10.0, azimuth_arc=10.0, azimuth_st
     _check_2d(dem, "sx_multi")
     keep, src, (ny, nx) = _source(dem)
     packs = _lib.pack_list(pack, [str(a) for a in azimuths])
-    if pack is not None:
-        outs, structs = [None] * len(sectors), [None] * len(sectors)
-        todo = []
-        for k, (window, _, _, dist) in enumerate(sectors):
-            if ny <= 2 * window or nx <= 2 * window or dist.size == 0 or np.all(np.isnan(dist)):
-                plane = np.zeros((ny, nx), dtype=np.float32)  # made on the host, like below
-                if ny > 2 * window and nx > 2 * window:
-                    plane[window : ny - window, window : nx - window] = np.nan
-                outs[k] = plane if packs[k] is None else _lib.encode_host(plane, packs[k])
-                continue
-            outs[k], structs[k] = _lib.result_plane(packs[k], (ny, nx))
-            todo.append(k)
-        if todo:
-            first, dj, di, dist, window = device.pack_sectors([sectors[k] for k in todo])
-            planes = _lib.plane_array([structs[k] for k in todo])
-            _lib.check(_lib.lib().topo_amd_sx_multi_packed(
-                src, ny, nx, len(todo), first.ctypes.data_as(_lib._i32p), dj.ctypes.data_as(_lib._i32p),
-                di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
-                float(height), planes), "topo_amd_sx_multi_packed")
-            for n, k in enumerate(todo):
-                outs[k] = _lib.wrap_plane(outs[k], planes[n], packs[k])
-        return [o if isinstance(o, _lib.PackedPlane) else o.astype(dem.dtype, copy=False) for o in outs]
-    outs = [np.zeros((ny, nx), dtype=np.float32) for _ in sectors]
-    # sectors the device has something to do for: the DEM is larger than the zero frame and there
-    # is a usable ray pixel (else zeros, or NaN inside the frame, as in _sx_rolling)
-    todo = []
-    for k, (window, _, _, dist) in enumerate(sectors):
-        if ny <= 2 * window or nx <= 2 * window:
-            continue
-        if dist.size == 0 or np.all(np.isnan(dist)):
-            outs[k][window : ny - window, window : nx - window] = np.nan
-            continue
-        todo.append(k)
+    # the sectors the device has work for (the others are made on the host, as in _sx_scan) go into one library call
+    outs = [_sx_host_plane((ny, nx), window, dist) for window, _, _, dist in sectors]
+    structs = [None] * len(sectors)
+    todo = [k for k, o in enumerate(outs) if o is None]
+    for k in todo:
+        outs[k], structs[k] = _lib.result_plane(packs[k], (ny, nx))
     if todo:
         first, dj, di, dist, window = device.pack_sectors([sectors[k] for k in todo])
-        planes = (C.c_void_p * len(todo))(*[_lib.ptr(outs[k]) for k in todo])
-        _lib.check(_lib.lib().topo_amd_sx_multi_raw(
+        planes = _lib.plane_array([structs[k] for k in todo])
+        _lib.check(_lib.lib().topo_amd_sx_multi_packed(
             src, ny, nx, len(todo), first.ctypes.data_as(_lib._i32p), dj.ctypes.data_as(_lib._i32p),
             di.ctypes.data_as(_lib._i32p), dist.ctypes.data_as(_lib._f64p), window.ctypes.data_as(_lib._i32p),
-            float(height), planes), "topo_amd_sx_multi_raw")
-    return [o.astype(dem.dtype, copy=False) for o in outs]
+            float(height), planes), "topo_amd_sx_multi_packed")
+        for n, k in enumerate(todo):
+            structs[k] = planes[n]  # (with the library's counters)
+    return [_sx_result(o, s, q, dem.dtype) for o, s, q in zip(outs, structs, packs)]
 
 
 # ---- valley / ridge index ---------------------------------------------------------------------
