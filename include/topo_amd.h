@@ -269,6 +269,32 @@ int topo_amd_gradient_dev(const float* in, int in_rows, int in_row0, int gny, in
                           const void* res_y, int out_row0, int out_rows, float* dx_out,
                           float* dy_out, float* slope_out, float* aspect_out);
 
+/* Valid-sample gradient: dx, dy, slope and aspect of a DEM with its gaps left open (csrc/gradient.hip, K4v; no reference
+ * counterpart - fill_na invents terrain along x, and in the plain call one NaN erases a disc of radius 4 sigma + 1).
+ * MISSING as above: not finite, or beyond +-2^24.
+ * sigma > 1.  q is topo_amd_gaussian_valid_dev(..., sigma, sigma, min_weight, fill = 1): N / D where D > 0 and D >= min_weight,
+ * undefined elsewhere - defined inside gaps wherever the window reaches a valid sample, so a valid pixel on a gap's rim still has
+ * both neighbours.  Along an axis, at a pixel where q is defined, the derivative is
+ *     (q[+1] - q[-1]) / 2       where both neighbours exist and are defined,
+ *     q[+1] - q[0] or q[0] - q[-1]   where only one of them does,
+ * and undefined where neither does or q[0] itself is not.  A raster edge is a neighbour that does not exist, so on a gap-free
+ * raster this is numpy.gradient of the Gaussian.  sig_ratio != 1: two such planes, dx from q(sigma sig_ratio, sigma) (axis 0,
+ * axis 1) and dy from q(sigma, sigma sig_ratio), each with its own D and the same min_weight.
+ * sigma <= 1.  The Sobel pair of topo_amd_sobel_dev (kernel / 8, true convolution, reflect at the global edges); dx is defined
+ * where all six samples under its non-zero taps are valid (a reflected tap is valid when the sample it lands on is), dy by the
+ * same rule with its own six taps; the centre is a tap of neither.  min_weight is accepted and ignored.
+ * Both.  All four outputs are NaN at a pixel whose own sample is missing unless fill != 0.  dx, dy, slope and aspect then follow
+ * from the arithmetic of topo_amd_gradient_dev (signed resolutions, the three resolution modes, aspect in [0, 360)); slope and
+ * aspect are NaN where dx or dy is, and no output is infinite.  Any output may be NULL; leaving one out does not change the others.
+ * Row blocks: the wider filter's radius + 1 ghost rows (1 for sigma <= 1), fewer are refused; the Gaussian's offsets sit on the
+ * global grid, so the bits do not depend on row blocks or out_row0 / out_rows.  topo_amd_gradient_route reports 5 (6 with
+ * sig_ratio != 1 at sigma > 1).
+ * A filter radius above 121 (sigma or sigma sig_ratio beyond 30.25): TOPO_AMD_EUNSUP.  A negative or NaN sigma, sig_ratio not
+ * positive, min_weight outside [0, 1] or NaN, fewer than 2 samples along an axis at sigma > 1: TOPO_AMD_EINVAL.             */
+int topo_amd_gradient_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, double sigma, double sig_ratio,
+                                double min_weight, int fill, int res_mode, const void* res_x, const void* res_y, int out_row0,
+                                int out_rows, float* dx_out, float* dy_out, float* slope_out, float* aspect_out);
+
 /* Sx max-elevation-angle scan (replaces topo._sx_rolling topo.py:928-953, called from :856).
  * dj/di: offsets of the ray pixels relative to the target (host int32, n_off entries,
  * duplicates allowed); dist: metric distance of each (host double, NaN = skip, as left by
@@ -370,7 +396,9 @@ int topo_amd_sx_route(int* route);
  *   bit 20       an _if epilogue was queued behind a deferred two-pass smooth (it runs only if the fused kernels of the
  *                chunks met a sample that is not a plain finite one).
  *   bit 21       the row chunks were tapered (first and last a quarter of the others).
- *   bits 22 - 28 the number of row chunks (0 unless Chunked).                                                             */
+ *   bits 22 - 28 the number of row chunks (0 unless Chunked).
+ * topo_amd_gradient_valid_dev and the calls built on it report route 5, or 6 for sig_ratio != 1 at sigma > 1 (two planes of the
+ * valid-sample Gaussian), with every other field 0.                                                                      */
 int topo_amd_gradient_route(int* route);
 /* Which kernels the calling thread's last TPI / STD disc call queued (topo_amd_tpi_std_dev, topo_amd_tpi_multi_dev and the
  * calls built on them; for tests and diagnostics): what the host decided, noted by the code that decided it once every
@@ -545,6 +573,11 @@ int topo_amd_fill_na_raw(const topo_amd_raster* src, int ny, int nx, const doubl
 int topo_amd_gradient_raw(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
                           const void* res_x, const void* res_y, float* dx_out, float* dy_out, float* slope_out,
                           float* aspect_out);
+/* topo_amd_gradient_valid_dev on a host raster, through the upload / decode / row-chunk pipeline of topo_amd_gradient_raw: a
+ * declared nodata is NaN behind the decode, hence a gap.  Errors as for the device call.                                   */
+int topo_amd_gradient_valid_raw(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, double min_weight,
+                                int fill, int res_mode, const void* res_x, const void* res_y, float* dx_out, float* dy_out,
+                                float* slope_out, float* aspect_out);
 int topo_amd_sx_raw(const topo_amd_raster* src, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist,
                     int n_off, int window, double height, float* out);
 int topo_amd_sx_multi_raw(const topo_amd_raster* src, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,
@@ -634,6 +667,11 @@ int topo_amd_gauss_valid_packed(const topo_amd_raster* src, int ny, int nx, doub
 int topo_amd_gradient_packed(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, int res_mode,
                              const void* res_x, const void* res_y, topo_amd_plane* dx_out, topo_amd_plane* dy_out,
                              topo_amd_plane* slope_out, topo_amd_plane* aspect_out);
+/* topo_amd_gradient_valid_raw with packed result planes: a NaN output (an undefined derivative, a missing pixel without fill)
+ * takes the plane's nodata code and is counted in `missing`.                                                                */
+int topo_amd_gradient_valid_packed(const topo_amd_raster* src, int ny, int nx, double sigma, double sig_ratio, double min_weight,
+                                   int fill, int res_mode, const void* res_x, const void* res_y, topo_amd_plane* dx_out,
+                                   topo_amd_plane* dy_out, topo_amd_plane* slope_out, topo_amd_plane* aspect_out);
 int topo_amd_sx_packed(const topo_amd_raster* src, int ny, int nx, const int32_t* dj, const int32_t* di, const double* dist,
                        int n_off, int window, double height, topo_amd_plane* out);
 int topo_amd_sx_multi_packed(const topo_amd_raster* src, int ny, int nx, int n_az, const int32_t* first, const int32_t* dj,

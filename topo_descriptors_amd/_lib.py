@@ -97,6 +97,12 @@ SIGNATURES = {
     "topo_amd_gradient_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                         C.c_double, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp,
                                         _vp, _vp]),
+    "topo_amd_gradient_valid_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                              C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "topo_amd_gradient_valid_raw": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "topo_amd_gradient_valid_packed": (C.c_int, [_rp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                 _vp, _vp, _pp, _pp, _pp, _pp]),
     "topo_amd_sx_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f64p,
                                   C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _vp]),
     "topo_amd_tpi_multi_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int,

@@ -8,6 +8,7 @@ scale.  The reference writes netCDF through xarray; here the writer is pluggable
 installed the same ``topo_<NAME>.nc`` files are produced, otherwise ``topo_<NAME>.npy``.  Every
 wrapper also returns ``{name: array}``.
 """
+import functools
 import logging
 import os
 
@@ -308,13 +309,19 @@ def compute_std(dem_ds, scales, smth_factors=None, ind_nans=(), crop=None, outdi
     return _tpi_std(dem_ds, scales, smth_factors, ind_nans, crop, outdir, "std", pack, skipna, min_count)
 
 
-def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdir=".", pack=None):
+def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdir=".", pack=None, skipna=False, min_weight=0.0,
+                     fill=False):
     """dx, dy, slope, aspect for every scale (reference topo.py:534-594).  ``pack``: a dict with the keys ``dx``, ``dy``,
     ``slope``, ``aspect`` (a missing key: float32), or one ``Packing`` for the four.  ``crop``, ``ind_nans``: see
     :func:`compute_dem`.  With 2-D per-pixel resolutions (a WGS84 grid) the gradient keeps its host-buffer call, which
     computes whole planes; when a mask or a crop is present that call is made at float32 and each plane's domain rows are
     uploaded again and finished by the same device call as everywhere else, so that the bits of a masked, cropped or packed
-    sample have one definition - an upload on a rare path."""
+    sample have one definition - an upload on a rare path.
+    ``skipna=True``: the gradient over the samples that exist (``topo.gradient(skipna=True)``: pass the DEM UNFILLED) with its
+    ``min_weight`` and ``fill``, on the resident DEM (``Block.gradient_valid``); ``crop``, ``ind_nans`` and ``pack`` are applied
+    afterwards as ever, output names are unchanged."""
+    min_weight = topo._valid_gauss_args(skipna, min_weight, fill, False, "compute_gradient")
+    valid_kw = {"skipna": True, "min_weight": min_weight, "fill": fill} if skipna else {}
     hlp.check_dem(dem_ds)
     packs = _lib.pack_list(pack, topo.GRADIENT_PLANES)
     logger.info("***Starting gradients computation for scales %s meters***", scales)
@@ -340,14 +347,17 @@ def compute_gradient(dem_ds, scales, sig_ratios=1, ind_nans=(), crop=None, outdi
         for scale, sigma, ratio in zip(scales, sigmas, sig_ratios):
             names = _gradient_names(scale, ratio)
             if two_d and plain:  # per-pixel resolutions (WGS84 grids): host-buffer entry point
-                arrays = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio, pack=None if pack is None else packs)
+                arrays = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio, pack=None if pack is None else packs, **valid_kw)
             elif two_d:
-                whole = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio)
+                whole = topo.gradient(dem_val, sigma, res_meters, sig_ratio=ratio, **valid_kw)
                 arrays = [fin.leave_host(a, q) for a, q in zip(whole, packs)]
                 arrays = [a.astype(w.dtype, copy=False) if q is None else a for a, w, q in zip(arrays, whole, packs)]
             else:
-                res.block.gradient(sigma, res_meters["x"], res_meters["y"], sig_ratio=ratio,
-                                   dx=outs[0], dy=outs[1], slope=outs[2], aspect=outs[3], **fin.rows_kw)
+                run = res.block.gradient
+                if skipna:
+                    run = functools.partial(res.block.gradient_valid, min_weight=min_weight, fill=fill)
+                run(sigma, res_meters["x"], res_meters["y"], sig_ratio=ratio,
+                    dx=outs[0], dy=outs[1], slope=outs[2], aspect=outs[3], **fin.rows_kw)
                 arrays = [fin.leave(o, q) for o, q in zip(outs, packs)]
             for array, name, unit in zip(arrays, names, units):
                 _emit(array, dem_ds, name, crop, outdir, unit, results)

@@ -290,6 +290,25 @@ int topo_amd_gradient_dev(const float* in, int in_rows, int in_row0, int gny, in
                            aspect_out);
 }
 
+int topo_amd_gradient_valid_dev(const float* in, int in_rows, int in_row0, int gny, int nx, double sigma, double sig_ratio,
+                                double min_weight, int fill, int res_mode, const void* res_x, const void* res_y, int out_row0,
+                                int out_rows, float* dx_out, float* dy_out, float* slope_out, float* aspect_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    TOPO_REQUIRE(sigma >= 0.0, "gradient_valid: negative sigma");  // (false for NaN)
+    TOPO_REQUIRE(sig_ratio > 0.0 && sig_ratio <= 1e6, "gradient_valid: sig_ratio %g (a positive factor)", sig_ratio);
+    TOPO_REQUIRE(min_weight >= 0.0 && min_weight <= 1.0, "gradient_valid: min_weight %g outside [0, 1]", min_weight);
+    Block b{in, in_rows, in_row0, gny, nx, out_row0, out_rows};
+    // ghost rows: the wider filter's radius and the row of the difference; 1 for the Sobel pair (beyond the radii of the
+    // valid-sample Gaussian the launcher refuses the call)
+    const double wide = sigma > 1.0 ? std::max(sigma, sigma * sig_ratio) : 0.0;
+    const int h = (int)std::min(4.0 * wide + 0.5, kGaussValidMaxRadius + 1.0) + 1;
+    TOPO_TRY(check_block(b, h, h, "gradient_valid"));
+    for (float* o : {dx_out, dy_out, slope_out, aspect_out}) forget_plane(o, out_rows, nx);
+    return launch_gradient_valid(b, sigma, sig_ratio, min_weight, fill != 0, res_mode, res_x, res_y, dx_out, dy_out, slope_out,
+                                 aspect_out);
+}
+
 int topo_amd_sx_dev(const float* in, int in_rows, int in_row0, int gny, int nx, const int32_t* dj,
                     const int32_t* di, const double* dist, int n_off, int window, double height,
                     int out_row0, int out_rows, float* out) {

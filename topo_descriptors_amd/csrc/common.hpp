@@ -221,6 +221,10 @@ int launch_sobel(const Block& b, float* dx_out, float* dy_out);
 int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode,
                     const void* res_x, const void* res_y, float* dx, float* dy, float* slope,
                     float* aspect);
+// the valid-sample gradient (gradient.hip, K4v): the difference that knows which neighbours exist over launch_gaussian_valid's
+// plane(s) taken with fill, the mask-aware Sobel pair for sigma <= 1; notes route 5 (6 with sig_ratio != 1)
+int launch_gradient_valid(const Block& b, double sigma, double sig_ratio, double min_weight, bool fill, int res_mode, const void* res_x,
+                          const void* res_y, float* dx, float* dy, float* slope, float* aspect);
 int launch_sx(const Block& b, const int32_t* dj, const int32_t* di, const double* dist,
               int n_off, int window, double height, float* out);
 // several azimuth sectors in one pass: sector a owns entries [first[a], first[a+1]) of the tables

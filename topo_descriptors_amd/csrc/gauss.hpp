@@ -27,6 +27,11 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
 // (x - NaN is NaN for every x of the group).
 __device__ __forceinline__ float finite_or_zero(float c) { return fabsf(c) <= 3.0e38f ? c : 0.0f; }
 
+// the valid-sample units (gauss_valid.hip, the valid-sample gradient of gradient.hip): at or beyond 2^24 (or not finite) a
+// sample is missing (disc_valid.hip)
+constexpr float kMissingLim = 16777216.0f;
+__device__ __forceinline__ bool sample_valid(float v) { return fabsf(v) < kMissingLim; }  // false for NaN / inf
+
 struct GaussArgs {
     const float* in;
     float* out;
@@ -111,6 +116,8 @@ struct GradNote {  // what the launchers decided, for topo_amd_gradient_route (g
 };
 extern thread_local GradNote t_grad;  // (defined in gradient.hip)
 constexpr int kGradFinishTiled = 1, kGradFinishWave = 2, kGradFinishUnfused = 3;
+// the route codes of the valid-sample gradient (launch_gradient_valid: no other field), behind GradRoute's 0 ... 4
+constexpr int kGradRouteValid = 5, kGradRouteValidAniso = 6;
 
 // the environment's switches, read by their callers once: on unless the variable starts with '0'; a number, or `unset`
 inline bool env_switch_on(const char* name) { const char* e = std::getenv(name); return !(e && *e == '0'); }

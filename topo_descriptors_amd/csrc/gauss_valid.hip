@@ -24,8 +24,6 @@ namespace topo {
 
 namespace {
 
-constexpr float kMissingLim = 16777216.0f;  // 2^24: at or beyond it (or not finite) a sample is missing (disc_valid.hip)
-__device__ __forceinline__ bool sample_valid(float v) { return fabsf(v) < kMissingLim; }  // false for NaN / inf
 // a raw sample as the two channels (m x, m)
 __device__ __forceinline__ float2 classify(float v) { return sample_valid(v) ? make_float2(v, 1.0f) : make_float2(0.0f, 0.0f); }
 

@@ -903,7 +903,201 @@ int gradient_slab(const Block& b, double sigma, double sig_ratio, int res_mode, 
     g.s_rows = s.out_rows;
     return noter.done(launch_epilogue(g, b.out_rows, c.compute));
 }
+// ---- K4v: the valid-sample gradient (topo.gradient(skipna=True), include/topo_amd.h: topo_amd_gradient_valid_dev) --------
+// sigma > 1: an epilogue over one or two planes q of the valid-sample Gaussian taken with fill (gauss_valid.hip), in which NaN
+// says "q is not defined here".  Along an axis the derivative at a pixel whose q is defined is the central difference / 2 where
+// both neighbours exist and are defined, the one-sided first-order difference where one of them does, NaN where neither does;
+// a raster edge is a neighbour that does not exist, so on a gap-free raster this is numpy.gradient.  sigma <= 1: the Sobel pair
+// where all six samples under the non-zero taps of a derivative are valid.  Both: NaN in every plane at a pixel whose own
+// sample is missing unless `fill`; then gradient_values, the arithmetic of every other route.
+struct ValidGradArgs {
+    GradArgs g;  // raw: the block itself (the epilogue reads it only when fill == 0); gx_src / gy_src: the q planes
+    int fill;
+};
+
+// selects only: the three cases are picked by v_cndmask on q == q, no lane takes a path of its own
+__device__ __forceinline__ float valid_difference(float qm, float q0, float qp) {
+    // (& and |, not && and ||: a short-circuit becomes an exec-masked region)
+    const bool hm = qm == qm, hp = qp == qp, h0 = q0 == q0;
+    const float d = ((hp ? qp : q0) - (hm ? qm : q0)) * ((hm & hp) ? 0.5f : 1.0f);
+    return (h0 & (hm | hp)) ? d : NAN;
+}
+
+// gradient_values behind the rule for a pixel's own sample; slope and aspect are NaN where dx or dy is
+__device__ __forceinline__ void valid_gradient_values(float& dx, float& dy, bool keep, float rx, float ry, float& slope, float& aspect) {
+    const bool has_dx = keep & (dx == dx), has_dy = keep & (dy == dy);
+    gradient_values(dx, dy, rx, ry, slope, aspect);
+    dx = has_dx ? dx : NAN;  // (one NaN, whatever the arithmetic made of its operand)
+    dy = has_dy ? dy : NAN;
+    slope = (has_dx & has_dy) ? slope : NAN;
+    aspect = (has_dx & has_dy) ? aspect : NAN;
+}
+
+__device__ __forceinline__ void valid_epilogue_pixel(const ValidGradArgs& a, int oy, int ox) {
+    const GradArgs& p = a.g;
+    const float* rowx = p.gx_src + (size_t)(oy - p.s_row0) * p.nx;
+    const float xm = rowx[max(ox - 1, 0)], xp = rowx[min(ox + 1, p.nx - 1)];  // (clamped loads, the edge is a select)
+    float dx = valid_difference(ox > 0 ? xm : NAN, rowx[ox], ox < p.nx - 1 ? xp : NAN);
+    const float* coly = p.gy_src + (size_t)(oy - p.s_row0) * p.nx + ox;
+    const float ym = coly[oy > 0 ? -p.nx : 0], yp = coly[oy < p.gny - 1 ? p.nx : 0];
+    float dy = valid_difference(oy > 0 ? ym : NAN, coly[0], oy < p.gny - 1 ? yp : NAN);
+    const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
+    const float own = a.fill ? 0.0f : p.raw[(size_t)(oy - p.raw_row0) * p.nx + ox];
+    float rx, ry, slope, aspect;
+    resolution_at(p, oy, ox, rx, ry);
+    valid_gradient_values(dx, dy, sample_valid(own), rx, ry, slope, aspect);
+    if (p.dx) p.dx[o] = dx;
+    if (p.dy) p.dy[o] = dy;
+    if (p.slope) p.slope[o] = slope;
+    if (p.aspect) p.aspect[o] = aspect;
+}
+
+// Built like gradient_epilogue4_kernel: four adjacent pixels a thread, 16-byte loads of the three q rows (and of the raw row
+// when fill == 0: 24 instead of 20 B / pixel) and 16-byte streaming stores, which need dword alignment only - any width; the
+// last 1 ... 3 pixels of a row (every pixel of a row under 4 columns) go one by one.
+__global__ __launch_bounds__(kThreads) void gradient_valid_epilogue4_kernel(ValidGradArgs a) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const GradArgs& p = a.g;
+    const int ox = (blockIdx.x * kThreads + threadIdx.x) * 4;
+    const int oy = p.out_row0 + blockIdx.y;
+    if (ox >= p.nx) return;
+    if (ox + 4 > p.nx) {
+        for (int x = ox; x < p.nx; ++x) valid_epilogue_pixel(a, oy, x);
+        return;
+    }
+    const float* rowx = p.gx_src + (size_t)(oy - p.s_row0) * p.nx;
+    const f4 mid = *reinterpret_cast<const f4*>(rowx + ox);
+    const float left = rowx[max(ox - 1, 0)], right = rowx[min(ox + 4, p.nx - 1)];
+    const float* coly = p.gy_src + (size_t)(oy - p.s_row0) * p.nx + ox;
+    const bool has_up = oy > 0, has_dn = oy < p.gny - 1;  // (block-uniform)
+    const f4 cen = *reinterpret_cast<const f4*>(coly);
+    const f4 up = *reinterpret_cast<const f4*>(coly - (has_up ? p.nx : 0));
+    const f4 dn = *reinterpret_cast<const f4*>(coly + (has_dn ? p.nx : 0));
+    // the pixels' own samples; with fill nobody asks, and the load goes to the row just fetched instead of the raw plane (an
+    // address chosen per block: a conditional load would put a wait for it in front of the arithmetic)
+    const bool fill = a.fill != 0;
+    const f4 own = *reinterpret_cast<const f4*>(fill ? coly : p.raw + (size_t)(oy - p.raw_row0) * p.nx + ox);
+    f4 odx, ody, osl, oas;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int x = ox + t;
+        const float xm = t == 0 ? (x > 0 ? left : NAN) : mid[t == 0 ? 0 : t - 1];
+        const float xp = t == 3 ? (x < p.nx - 1 ? right : NAN) : mid[t == 3 ? 3 : t + 1];
+        float dx = valid_difference(xm, mid[t], xp);
+        float dy = valid_difference(has_up ? up[t] : NAN, cen[t], has_dn ? dn[t] : NAN);
+        float rx, ry, slope, aspect;
+        resolution_at(p, oy, x, rx, ry);
+        valid_gradient_values(dx, dy, fill | sample_valid(own[t]), rx, ry, slope, aspect);
+        odx[t] = dx;
+        ody[t] = dy;
+        osl[t] = slope;
+        oas[t] = aspect;
+    }
+    const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
+    if (p.dx) __builtin_nontemporal_store(odx, reinterpret_cast<f4*>(p.dx + o));
+    if (p.dy) __builtin_nontemporal_store(ody, reinterpret_cast<f4*>(p.dy + o));
+    if (p.slope) __builtin_nontemporal_store(osl, reinterpret_cast<f4*>(p.slope + o));
+    if (p.aspect) __builtin_nontemporal_store(oas, reinterpret_cast<f4*>(p.aspect + o));
+}
+
+// sobel_kernel with a mask: a missing sample enters the sums as 0 and takes away the derivatives it has a tap in (the centre
+// has a tap in neither).  On a raster without gaps: the bits of sobel_kernel<true>.
+__global__ __launch_bounds__(kThreads) void sobel_valid_kernel(ValidGradArgs a) {
+    const GradArgs& p = a.g;
+    const int ox = blockIdx.x * kThreads + threadIdx.x;
+    const int oy = p.out_row0 + blockIdx.y;
+    if (ox >= p.nx) return;
+    bool has_dx = true, has_dy = true;
+    auto tap = [&](int gy, int gx, bool in_dx, bool in_dy) -> double {
+        const double v = raw_reflect(p, gy, gx);
+        const bool ok = fabs(v) < (double)kMissingLim;  // (the float32 sample, widened exactly)
+        has_dx = has_dx && (ok || !in_dx);
+        has_dy = has_dy && (ok || !in_dy);
+        return ok ? v : 0.0;
+    };
+    const double nw = tap(oy - 1, ox - 1, true, true), n = tap(oy - 1, ox, false, true), ne = tap(oy - 1, ox + 1, true, true);
+    const double w = tap(oy, ox - 1, true, false), e = tap(oy, ox + 1, true, false);
+    const double sw = tap(oy + 1, ox - 1, true, true), s = tap(oy + 1, ox, false, true), se = tap(oy + 1, ox + 1, true, true);
+    float dx = has_dx ? (float)(0.125 * (ne - nw) + 0.25 * (e - w) + 0.125 * (se - sw)) : NAN;
+    float dy = has_dy ? (float)(0.125 * (sw - nw) + 0.25 * (s - n) + 0.125 * (se - ne)) : NAN;
+    const size_t o = (size_t)(oy - p.out_row0) * p.nx + ox;
+    const bool keep = a.fill || sample_valid(p.raw[(size_t)(oy - p.raw_row0) * p.nx + ox]);
+    float rx, ry, slope, aspect;
+    resolution_at(p, oy, ox, rx, ry);
+    valid_gradient_values(dx, dy, keep, rx, ry, slope, aspect);
+    if (p.dx) p.dx[o] = dx;
+    if (p.dy) p.dy[o] = dy;
+    if (p.slope) p.slope[o] = slope;
+    if (p.aspect) p.aspect[o] = aspect;
+}
+
+// the valid-sample gradient of a block no taller than a launch covers
+int gradient_valid_slab(const Block& b, double sigma, double sig_ratio, double min_weight, bool fill, int res_mode, const void* res_x,
+                        const void* res_y, float* dx, float* dy, float* slope, float* aspect) {
+    Context& c = ctx();
+    ValidGradArgs a{};
+    GradArgs& g = a.g;
+    TOPO_TRY(upload_resolution(res_mode, res_x, res_y, b.nx, b.gny, &g.res_x, &g.res_y));
+    g.res_mode = res_mode;
+    g.raw = b.in;
+    g.raw_rows = b.in_rows;
+    g.raw_row0 = b.in_row0;
+    g.gny = b.gny;
+    g.nx = b.nx;
+    g.out_row0 = b.out_row0;
+    g.out_rows = b.out_rows;
+    g.dx = dx;
+    g.dy = dy;
+    g.slope = slope;
+    g.aspect = aspect;
+    a.fill = fill ? 1 : 0;
+    TOPO_TRY(check_grid_rows(b.out_rows, "valid-sample sobel / gradient epilogue"));
+    if (sigma <= 1.0) return launch(sobel_valid_kernel, dim3((b.nx + kThreads - 1) / kThreads, b.out_rows), dim3(kThreads), 0, c.compute, a);
+    // q over the output rows and one neighbour row inside the raster, where launch_gradient keeps its smoothed planes
+    const Block s = smoothed_rows_block(b);
+    const size_t bytes = (size_t)s.out_rows * b.nx * sizeof(float);
+    void *plane_a = nullptr, *plane_b = nullptr;
+    TOPO_TRY(workspace(1, bytes, &plane_a));
+    if (sig_ratio == 1.0) {
+        TOPO_TRY(launch_gaussian_valid(s, sigma, sigma, min_weight, true, (float*)plane_a, nullptr));
+        plane_b = plane_a;
+    } else {  // dx of the field smoothed with sigma * sig_ratio down the columns, dy of the one smoothed with it along the rows
+        const double perp = sigma * sig_ratio;
+        TOPO_TRY(workspace(2, bytes, &plane_b));
+        TOPO_TRY(launch_gaussian_valid(s, perp, sigma, min_weight, true, (float*)plane_a, nullptr));
+        TOPO_TRY(launch_gaussian_valid(s, sigma, perp, min_weight, true, (float*)plane_b, nullptr));
+    }
+    g.gx_src = (const float*)plane_a;
+    g.gy_src = (const float*)plane_b;
+    g.s_row0 = s.out_row0;
+    g.s_rows = s.out_rows;
+    const dim3 grid(((b.nx + 3) / 4 + kThreads - 1) / kThreads, b.out_rows);
+    return launch(gradient_valid_epilogue4_kernel, grid, dim3(kThreads), 0, c.compute, a);
+}
 }  // namespace
+
+int launch_gradient_valid(const Block& b, double sigma, double sig_ratio, double min_weight, bool fill, int res_mode, const void* res_x,
+                          const void* res_y, float* dx, float* dy, float* slope, float* aspect) {
+    TOPO_REQUIRE(res_mode >= 0 && res_mode <= 2, "gradient_valid: bad res_mode %d", res_mode);
+    TOPO_REQUIRE(res_x && res_y, "gradient_valid: resolution arrays are NULL");
+    if (sigma > 1.0) TOPO_REQUIRE(b.gny >= 2 && b.nx >= 2, "gradient_valid: a finite difference needs at least 2 samples per axis (got %d x %d)", b.gny, b.nx);
+    if (ctx().ghost.armed) return TOPO_AMD_EUNSUP;  // (a row shard whose exchange is in flight: this call is not sharded)
+    TOPO_TRY(for_row_slabs(b.out_rows, [&](int r, int n) -> int {
+        Block s = b;
+        s.out_row0 = b.out_row0 + r;
+        s.out_rows = n;
+        const size_t shift = (size_t)r * b.nx;
+        const void *rx = res_x, *ry = res_y;
+        if (res_mode == TOPO_AMD_RES_2D) {
+            rx = (const float*)res_x + shift;
+            ry = (const float*)res_y + shift;
+        }
+        return gradient_valid_slab(s, sigma, sig_ratio, min_weight, fill, res_mode, rx, ry, dx ? dx + shift : nullptr, dy ? dy + shift : nullptr,
+                                   slope ? slope + shift : nullptr, aspect ? aspect + shift : nullptr);
+    }));
+    note_gradient_route(sigma > 1.0 && sig_ratio != 1.0 ? kGradRouteValidAniso : kGradRouteValid);
+    return TOPO_AMD_OK;
+}
 
 int launch_gradient(const Block& b, double sigma, double sig_ratio, int res_mode, const void* res_x, const void* res_y, float* dx,
                     float* dy, float* slope, float* aspect) {

@@ -792,6 +792,54 @@ int topo_amd_gradient_packed(const topo_amd_raster* raster, int ny, int nx, doub
     });
 }
 
+// the valid-sample gradient (gradient.hip, K4v) through the same pipeline: a declared nodata is NaN behind the decode, hence a gap
+int topo_amd_gradient_valid_raw(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio, double min_weight,
+                                int fill, int res_mode, const void* res_x, const void* res_y, float* dx_out, float* dy_out,
+                                float* slope_out, float* aspect_out) {
+    topo_amd_plane dx = f32_plane(dx_out), dy = f32_plane(dy_out), slope = f32_plane(slope_out), aspect = f32_plane(aspect_out);
+    return topo_amd_gradient_valid_packed(raster, ny, nx, sigma, sig_ratio, min_weight, fill, res_mode, res_x, res_y, &dx, &dy, &slope,
+                                          &aspect);
+}
+
+int topo_amd_gradient_valid_packed(const topo_amd_raster* raster, int ny, int nx, double sigma, double sig_ratio, double min_weight,
+                                   int fill, int res_mode, const void* res_x, const void* res_y, topo_amd_plane* dx_out,
+                                   topo_amd_plane* dy_out, topo_amd_plane* slope_out, topo_amd_plane* aspect_out) {
+    TOPO_ENTER();
+    TOPO_TRY(require_ready());
+    HostCall call;
+    TOPO_TRY(call.open(raster, ny, nx, "gradient_valid"));
+    TOPO_REQUIRE(sigma >= 0.0, "gradient_valid: negative sigma");
+    TOPO_REQUIRE(sig_ratio > 0.0 && sig_ratio <= 1e6, "gradient_valid: sig_ratio %g (a positive factor)", sig_ratio);
+    TOPO_REQUIRE(min_weight >= 0.0 && min_weight <= 1.0, "gradient_valid: min_weight %g outside [0, 1]", min_weight);
+    topo_amd_plane* planes[4] = {dx_out, dy_out, slope_out, aspect_out};
+    float* d_o[4];
+    for (int k = 0; k < 4; ++k) TOPO_TRY(call.plane(planes[k], &d_o[k]));
+    const void *rx = res_x, *ry = res_y;
+    if (res_mode == TOPO_AMD_RES_2D) {  // the call's extras: the two resolution planes on the device
+        TOPO_REQUIRE(res_x && res_y, "gradient_valid: resolution arrays are NULL");
+        float *d_rx, *d_ry;
+        TOPO_TRY(call.extra(&d_rx));
+        TOPO_TRY(call.extra(&d_ry));
+        TOPO_HIP(hipMemcpyAsync(d_rx, res_x, call.samples() * sizeof(float), hipMemcpyHostToDevice, ctx().compute));
+        TOPO_HIP(hipMemcpyAsync(d_ry, res_y, call.samples() * sizeof(float), hipMemcpyHostToDevice, ctx().compute));
+        rx = d_rx;
+        ry = d_ry;
+    }
+    // the radius of the wider filter and the row of the difference: all the ghost rows the device call wants
+    const double wide = sigma > 1.0 ? std::max(sigma, sigma * sig_ratio) : 0.0;
+    const int below = (int)std::min(4.0 * wide + 0.5, kGaussValidMaxRadius + 1.0) + 1;
+    return call.run(below, kRowChunks, [&](const Block& v, int r0) {
+        const void *cx = rx, *cy = ry;
+        if (res_mode == TOPO_AMD_RES_2D) {  // [out_rows x nx], aligned with the output rows
+            cx = (const float*)rx + (size_t)r0 * nx;
+            cy = (const float*)ry + (size_t)r0 * nx;
+        }
+        return topo_amd_gradient_valid_dev(v.in, v.in_rows, v.in_row0, v.gny, v.nx, sigma, sig_ratio, min_weight, fill, res_mode, cx, cy,
+                                           r0, v.out_rows, call.at(d_o[0], r0), call.at(d_o[1], r0), call.at(d_o[2], r0),
+                                           call.at(d_o[3], r0));
+    });
+}
+
 int topo_amd_sx_raw(const topo_amd_raster* raster, int ny, int nx, const int32_t* dj, const int32_t* di,
                     const double* dist, int n_off, int window, double height, float* out) {
     topo_amd_plane o = f32_plane(out);

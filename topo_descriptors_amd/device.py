@@ -232,7 +232,8 @@ def gradient_route():
     axis 0), bit 6 Aniso with passes on both kinds of kernel, bits 7 - 11 the f16 step count; bits 12 - 13 the axis-1 finish of
     the Valu route (1 LDS-tiled, 2 wave-shift, 3 unfused), bit 14 its tap chunks of 16, bits 15 - 17 its PF; bits 18 - 19 the
     stand-alone epilogue (1 one pixel a thread, 2 four), bit 20 an ``_if`` rerun queued; bit 21 tapered chunks, bits 22 - 28
-    the number of row chunks."""
+    the number of row chunks.  A valid-sample call (``skipna=True``, ``Block.gradient_valid``) reports route 5, or 6 with
+    ``sig_ratio != 1`` at ``sigma > 1``, and nothing else."""
     n = C.c_int32()
     _lib.check(_lib.lib().topo_amd_gradient_route(C.byref(n)), "gradient_route")
     return n.value
@@ -375,6 +376,23 @@ class Block:
         _lib.check(_lib.lib().topo_amd_gradient_dev(*self._head(), float(sigma), float(sig_ratio),
                                                     mode, _lib.ptr(rx), _lib.ptr(ry), o0, on, *p),
                    "gradient_dev")
+
+    def gradient_valid(self, sigma, res_x, res_y, sig_ratio=1.0, min_weight=0.0, fill=False, dx=None, dy=None, slope=None,
+                       aspect=None, out_row0=None, out_rows=None):
+        """The gradient over the samples that exist (``topo_amd_gradient_valid_dev``; ``topo.gradient(skipna=True)`` for the
+        rules): differences of the valid-sample Gaussian taken with ``fill`` that know which of their neighbours are defined,
+        the mask-aware Sobel pair for ``sigma <= 1``; all four planes NaN at a missing pixel unless ``fill``.  Radii up to
+        121; ghost rows: the wider filter's radius + 1 (1 for ``sigma <= 1``).  Any plane may be left out."""
+        o0, on = self._range(out_row0, out_rows)
+        rx = np.ascontiguousarray(res_x, dtype=np.float64)
+        ry = np.ascontiguousarray(res_y, dtype=np.float64)
+        mode = _lib.RES_SCALAR if rx.size == 1 and ry.size == 1 else _lib.RES_1D
+        if mode == _lib.RES_1D:
+            assert rx.size == self.nx and ry.size == self.gny
+        p = [a.ptr if a else None for a in (dx, dy, slope, aspect)]
+        _lib.check(_lib.lib().topo_amd_gradient_valid_dev(*self._head(), float(sigma), float(sig_ratio), float(min_weight),
+                                                          int(bool(fill)), mode, _lib.ptr(rx), _lib.ptr(ry), o0, on, *p),
+                   "gradient_valid_dev")
 
     def sx(self, dj, di, dist, window, height, out, out_row0=None, out_rows=None):
         o0, on = self._range(out_row0, out_rows)

@@ -280,14 +280,26 @@ def dem(dem, sigma, pack=None, skipna=False, min_weight=0.0, fill=False, return_
     return (out, weight) if return_weight else out
 
 
-def sobel(dem):
-    """Sobel derivative pair (dx, dy), kernel / 8, reflect boundary (reference topo.py:658-685)."""
+def sobel(dem, skipna=False, fill=False):
+    """Sobel derivative pair (dx, dy), kernel / 8, reflect boundary (reference topo.py:658-685).
+
+    ``skipna=True``: over the samples that exist.  ``dx`` is defined where all six samples under its non-zero taps are valid
+    (finite and within +-2**24; a reflected tap is valid when the sample it lands on is), ``dy`` by the same rule with its own
+    six taps, NaN elsewhere; the centre is a tap of neither, and both are NaN at a pixel whose own sample is missing unless
+    ``fill=True``.  On a raster without gaps: the bits of the plain call.  ``fill`` without ``skipna`` is a ``ValueError``."""
+    _valid_gauss_args(skipna, 0.0, fill, False, "sobel")
     values, _ = _unwrap(dem)
     _check_2d(values, "sobel")
     keep, src, shape = _source(values)
     dx = _plane(shape)
     dy = _plane(shape)
     lib = _lib.lib()
+    if skipna:  # the Sobel route of the valid-sample gradient at a resolution of 1: dx / 1 and dy / 1 are dx and dy
+        one = np.ones(1, dtype=np.float64)
+        _lib.check(lib.topo_amd_gradient_valid_raw(src, shape[0], shape[1], 0.0, 1.0, 0.0, int(bool(fill)), _lib.RES_SCALAR,
+                                                   _lib.ptr(one), _lib.ptr(one), _lib.ptr(dx), _lib.ptr(dy), None, None),
+                   "topo_amd_gradient_valid_raw")
+        return dx, dy
     _lib.check(lib.topo_amd_sobel_raw(src, shape[0], shape[1], _lib.ptr(dx),
                                       _lib.ptr(dy)), "topo_amd_sobel_raw")
     return dx, dy
@@ -315,8 +327,19 @@ def _resolution_args(res_meters, shape):
 GRADIENT_PLANES = ("dx", "dy", "slope", "aspect")
 
 
-def gradient(dem, sigma, res_meters, sig_ratio=1, pack=None):
+def gradient(dem, sigma, res_meters, sig_ratio=1, pack=None, skipna=False, min_weight=0.0, fill=False):
     """[dx, dy, slope, aspect] of the Gaussian-smoothed DEM (reference topo.py:598-644).
+
+    ``skipna=True``: over the samples that exist - pass the DEM UNFILLED, its gaps as NaN or as the declared fill value of a
+    ``PackedDem``.  ``sigma > 1``: with ``q`` the Gaussian of :func:`dem` ``(skipna=True, fill=True)`` under this call's
+    ``min_weight``, the derivative along an axis at a pixel where ``q`` is defined is ``(q[+1] - q[-1]) / 2`` where both
+    neighbours exist and are defined, ``q[+1] - q[0]`` or ``q[0] - q[-1]`` where one of them does, NaN where neither does; a
+    raster edge is a neighbour that does not exist, so without gaps this is ``np.gradient`` of the Gaussian.  ``q`` is defined
+    inside a gap wherever the window reaches a valid sample: a valid pixel on a gap's rim keeps both neighbours.
+    ``sig_ratio != 1``: ``dx`` and ``dy`` from two such planes, as below.  ``sigma <= 1``: :func:`sobel` ``(skipna=True)``,
+    ``min_weight`` ignored.  All four planes are NaN at a pixel whose own sample is missing unless ``fill=True``; slope and
+    aspect are NaN where ``dx`` or ``dy`` is; nothing is infinite.  Radii up to 121.  Without ``skipna`` the kernels and bits
+    are the ones described below, and ``min_weight`` and ``fill`` are a ``ValueError``.
 
     ``sigma <= 1`` uses the Sobel pair; ``sig_ratio != 1`` smooths with ``sigma*sig_ratio``
     perpendicular to each derivative.  Derivatives are divided by the signed grid
@@ -326,14 +349,21 @@ def gradient(dem, sigma, res_meters, sig_ratio=1, pack=None):
 
     ``pack``: one :class:`Packing` for the four planes, a sequence of four, or a dict with the keys ``dx``, ``dy``, ``slope``,
     ``aspect`` (``None`` or a missing key: that plane stays float32); packed planes come back as :class:`PackedPlane`."""
+    min_weight = _valid_gauss_args(skipna, min_weight, fill, False, "gradient")
     values, _ = _unwrap(dem)
     _check_2d(values, "gradient")
     packs = _lib.pack_list(pack, GRADIENT_PLANES)
     keep, src, shape = _source(values)
     mode, rx, ry = _resolution_args(res_meters, shape)
     made = [_lib.result_plane(q, shape) for q in packs]
-    _lib.check(_lib.lib().topo_amd_gradient_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), mode, _lib.ptr(rx),
-                                                   _lib.ptr(ry), *[C.byref(m[1]) for m in made]), "topo_amd_gradient_packed")
+    refs = [C.byref(m[1]) for m in made]
+    if skipna:
+        _lib.check(_lib.lib().topo_amd_gradient_valid_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), min_weight,
+                                                             int(bool(fill)), mode, _lib.ptr(rx), _lib.ptr(ry), *refs),
+                   "topo_amd_gradient_valid_packed")
+    else:
+        _lib.check(_lib.lib().topo_amd_gradient_packed(src, shape[0], shape[1], float(sigma), float(sig_ratio), mode, _lib.ptr(rx),
+                                                       _lib.ptr(ry), *refs), "topo_amd_gradient_packed")
     return [_lib.wrap_plane(*m, q) for m, q in zip(made, packs)]
 
 
